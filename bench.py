@@ -48,6 +48,10 @@ def parse():
     ap.add_argument("--no-nested", action="store_true",
                     help="only the headline workload (default: the other workloads of BASELINE.json's "
                          "metric run after it and are reported under \"workloads\")")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed (its loss and "
+                         "the updated model state, a fixed sample of the large tensors) as DIR/<name>.npy; with several "
+                         "ranks, rank 0's (for DLRM: the tables rank 0 holds)")
     return ap.parse_args()
 
 
@@ -129,6 +133,15 @@ class DlrmWorkload:
     def step(self):
         self.trainer.set_lr_factor(self.sched.step())
         self.loss = self.trainer.train_step(self.num, self.cat, self.click)
+
+    def extra_outputs(self):
+        """For --dump-outputs: the embedding rows the first 64 samples of the batch looked up (and the step updated) -- a sample
+        of the [sum N_t, 128] table at fixed positions would almost never meet a row the step touched."""
+        emb = self.model.bottom_model.embeddings
+        if emb is None or self.cat is None:
+            return {}
+        rows = (self.cat[:64] + emb.offsets[:-1]).reshape(-1)
+        return {"embedding_rows_of_batch": emb.weight.detach()[rows].float().cpu().numpy()}
 
     def config(self):
         return {"workload": "DLRM Criteo-shape (criteo_f15 cardinalities, 26 tables x dim 128, 13 numerical), "
@@ -746,6 +759,36 @@ def sample_shader_clock(wl, steps, sample=True):
             "source": "torch.cuda.clock_rate() (amdsmi current gfx clock) every 20 ms over %d untimed steps" % steps}
 
 
+DUMP_SAMPLE = 16384              # elements kept of a larger state tensor (--dump-outputs)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, d):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy in float32: `loss` (what train_step returned) and
+    `state.<key>` for every floating tensor of the model's state_dict() after the step's update -- whole up to DUMP_SAMPLE
+    elements, else DUMP_SAMPLE elements at positions drawn by a generator seeded with the tensor's size (the same positions in
+    every run) -- plus the workload's extra_outputs().  Called outside the timed region, before any further step."""
+    import numpy as np
+    out = {"loss": wl.loss.detach().float().cpu().numpy().reshape(-1)}
+    for k, v in wl.model.state_dict().items():
+        if not v.is_floating_point():
+            continue
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(flat.numel()))
+            flat = flat[idx.to(flat.device)]
+        out["state." + k] = flat.float().cpu().numpy()
+    extra = getattr(wl, "extra_outputs", None)
+    if extra is not None:
+        out.update(extra())
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes for %s, more than the %d allowed" % (total, wl.name, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def run_workload(name, args, rank, world, device, steps, warmup):
     """Build the workload, warm up, time exactly `steps` steps (barrier + synchronize on both sides, nothing else
     inside), then the instrumented pass for the roofline.  Returns the record of this workload (rank 0) or None."""
@@ -768,6 +811,8 @@ def run_workload(name, args, rank, world, device, steps, warmup):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
     sclk = None
     if os.environ.get("DLE_BENCH_SCLK", "1") == "1":
         sclk = sample_shader_clock(wl, max(2, min(steps, 10)), sample=rank == 0)
@@ -962,6 +1007,7 @@ def main():
     import copy
     nargs = copy.copy(args)
     nargs.batch = nargs.dtype = nargs.max_table_size = None       # nested records always run their BASELINE config
+    nargs.dump_outputs = None                                     # (--dump-outputs: the headline workload only)
     dog = Watchdog(emit, rank) if nested_names else None
     for w in nested_names:
         st, wu = NESTED_STEPS[w]

@@ -681,8 +681,115 @@ def gen_tacotron2_frontend():
     print("tacotron2_frontend.npz", {k: v.shape for k, v in arrs.items() if not k.startswith("seq")})
 
 
+EXPR = "<expression>"           # an add_argument / DEFINE_* keyword whose value is not a literal (not comparable)
+
+
+def _literal(node):
+    import ast
+    try:
+        v = ast.literal_eval(node)
+    except Exception:
+        return EXPR
+    return sorted(v) if isinstance(v, set) else list(v) if isinstance(v, tuple) else v
+
+
+def _argparse_flags(*paths):
+    """{flag: {action, default, choices}} of every add_argument("--flag", ...) call in `paths` (ast, no import)."""
+    import ast
+    out = {}
+    for path in paths:
+        for node in ast.walk(ast.parse(open(path).read())):
+            if isinstance(node, ast.Call) and getattr(node.func, "attr", None) == "add_argument":
+                kw = {k.arg: _literal(k.value) for k in node.keywords if k.arg in ("action", "default", "choices")}
+                for a in node.args:
+                    if isinstance(a, ast.Constant) and isinstance(a.value, str) and a.value.startswith("--"):
+                        out[a.value] = kw
+    return out
+
+
+def gen_reference_interfaces():
+    """reference_interfaces.json: the reference's command-line flags (names, defaults, choices, switches) of the five entry points,
+    the DLRM module signatures, PolyWarmUpScheduler's first learning rates and the reference's roc_auc_score on two seeded cases --
+    what tests/test_entry_points.py and tests/test_dlrm_host.py compare this library with."""
+    import ast
+    import re
+    ref = os.path.join(R.REF, "PyTorch")
+    conv = os.path.join(ref, "Classification/ConvNets/main.py")
+    bert = os.path.join(ref, "LanguageModeling/BERT/run_pretraining.py")
+    dlrm = os.path.join(ref, "Recommendation/DLRM/dlrm/scripts/main.py")
+    speech = os.path.join(ref, "SpeechSynthesis/Tacotron2")
+    doc = {"flags": {"convnets": _argparse_flags(conv), "bert": _argparse_flags(bert)}, "flag_names": {}}
+    for m in ("tacotron2", "waveglow"):
+        doc["flags"][m] = _argparse_flags(os.path.join(speech, "train.py"), os.path.join(speech, m, "arg_parser.py"))
+    defines = []
+    for node in ast.walk(ast.parse(open(dlrm).read())):          # absl DEFINE_<kind>(name, default, ...)
+        if isinstance(node, ast.Call) and getattr(node.func, "attr", "").startswith("DEFINE_"):
+            kw = {k.arg: _literal(k.value) for k in node.keywords}
+            pos = [_literal(a) for a in node.args]
+            kind = node.func.attr[len("DEFINE_"):]
+            defines.append({"name": pos[0] if pos else kw["name"], "kind": kind,
+                            "default": kw["default"] if "default" in kw else pos[1],
+                            "choices": kw.get("enum_values", pos[2] if len(pos) > 2 else None) if kind == "enum" else None})
+    doc["flags"]["dlrm"] = defines
+    # flag NAMES as the reference's parsers spell them (regular expressions over the sources)
+    names = doc["flag_names"]
+    src = open(conv).read()
+    names["convnets"] = re.findall(r'"(--[a-zA-Z0-9_-]+)"', src[src.index("def add_parser_arguments"):src.index("def prepare_for_training")])
+    names["bert"] = re.findall(r"""add_argument\(\s*['"](--[a-zA-Z0-9_-]+)['"]""", open(bert).read())
+    src = open(dlrm).read()
+    names["dlrm"] = re.findall(r'DEFINE_[a-z]+\(\s*"([a-zA-Z0-9_]+)"', src)
+    names["dlrm_booleans"] = re.findall(r'DEFINE_boolean\(\s*"([a-zA-Z0-9_]+)"', src)
+    common = re.findall(r"""add_argument\(\s*(?:'-[a-z]+',\s*)?'(--[a-zA-Z0-9_-]+)'""",
+                        "\n".join(l for l in open(os.path.join(speech, "train.py")) if not l.lstrip().startswith("#")))
+    for m in ("tacotron2", "waveglow"):
+        names[m] = common + re.findall(r"""add_argument\(\s*'(--[a-zA-Z0-9_-]+)'""", open(os.path.join(speech, m, "arg_parser.py")).read())
+    names = {k: sorted(set(v)) for k, v in names.items()}
+    doc["flag_names"] = names
+    # DLRM modules: argument names in order (model/distributed.py, nn/parts.py)
+    sig = {}
+    root = os.path.join(ref, "Recommendation/DLRM/dlrm")
+    for path, cls, fn in (("model/distributed.py", "DistributedDlrm", "__init__"), ("model/distributed.py", "DistributedDlrm", "forward"),
+                          ("nn/parts.py", "DlrmBottom", "__init__"), ("nn/parts.py", "DlrmBottom", "forward"),
+                          ("nn/parts.py", "DlrmTop", "__init__")):
+        for n in ast.walk(ast.parse(open(os.path.join(root, path)).read())):
+            if isinstance(n, ast.ClassDef) and n.name == cls:
+                for f in n.body:
+                    if isinstance(f, ast.FunctionDef) and f.name == fn:
+                        sig["%s.%s" % (cls, fn)] = [a.arg for a in f.args.args[1:]]
+    doc["dlrm_signatures"] = sig
+    # BERT schedulers.py PolyWarmUpScheduler (base 6e-3, warm-up 0.2843, 40 steps), stepped before the optimizer for k = 0..10
+    sys.path.insert(0, os.path.join(ref, "LanguageModeling/BERT"))
+    try:
+        import schedulers as RS
+    finally:
+        sys.path.pop(0)
+    p = torch.nn.Parameter(torch.zeros(1))
+    opt = torch.optim.SGD([p], lr=6e-3)
+    sch = RS.PolyWarmUpScheduler(opt, warmup=0.2843, total_steps=40, base_lr=6e-3, device="cpu")
+    lrs = []
+    for k in range(0, 11):
+        opt.param_groups[0]["step"] = torch.tensor(float(k))
+        sch.step()
+        lrs.append(float(opt.param_groups[0]["lr"]))
+    doc["bert_poly_warmup_lr"] = {"base_lr": 6e-3, "warmup": 0.2843, "total_steps": 40, "lr": lrs}
+    # DLRM dlrm/scripts/utils.py roc_auc_score (the function alone: the module imports dllogger) on the first two seeded cases of
+    # tests/test_dlrm_host.py::test_roc_auc_matches_sklearn_and_reference
+    src = open(os.path.join(root, "scripts/utils.py")).read()
+    ns = {"torch": torch}
+    exec(compile(src[src.index("def roc_auc_score"):], "utils.py", "exec"), ns)
+    g = torch.Generator().manual_seed(0)
+    y = (torch.rand(5000, generator=g) < 0.3).float()
+    cases = [(y, torch.randn(5000, generator=g) + y), (y, torch.randint(0, 7, (5000,), generator=g).float())]
+    doc["dlrm_roc_auc"] = [float(ns["roc_auc_score"](yt.clone(), ys.clone())) for yt, ys in cases]
+    with open(os.path.join(GOLD, "reference_interfaces.json"), "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("reference_interfaces.json", {k: len(v) for k, v in doc["flags"].items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["dlrm", "dlrm_step", "rn50", "lamb", "bert", "floors", "waveglow", "tacotron2", "tacotron2_frontend"]
+    which = sys.argv[1:] or ["dlrm", "dlrm_step", "rn50", "lamb", "bert", "floors", "waveglow", "tacotron2", "tacotron2_frontend",
+                             "reference_interfaces"]
     os.makedirs(GOLD, exist_ok=True)
     if not R.have_reference():
         sys.exit("reference not mounted; fixtures are generated in the build container only")

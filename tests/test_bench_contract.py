@@ -121,3 +121,94 @@ def test_line_says_where_traffic_comes_from_and_which_process_group_ran():
     assert src is not None and "profiles/traffic.json" in src and "round" in src and "not measured in this run" in src
     info = bench.comm_info()                                           # no process group in this test
     assert (info["backend"], info["world"], info["ranks_seen"]) == (None, 1, 1) and "torch.distributed" in info["path"]
+
+
+def test_dump_outputs_writes_the_loss_and_a_fixed_sample_of_the_state(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/loss.npy and DIR/state.<key>.npy (float32) for every floating tensor of the model's state; a tensor
+    larger than DUMP_SAMPLE is sampled at the same positions in every run; integer buffers are left out; the workload's
+    extra_outputs() are added; more than the byte limit is refused."""
+    import numpy as np
+    import pytest
+    import torch
+
+    class Wl:
+        name = "fake"
+
+        def __init__(self, seed):
+            torch.manual_seed(seed)
+            self.model = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.BatchNorm1d(200))
+            self.loss = torch.tensor([0.25 + seed])
+
+        def extra_outputs(self):
+            return {"extra": np.arange(3, dtype=np.float32)}
+
+    assert "--dump-outputs" in open(os.path.join(ROOT, "bench.py")).read()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "x")])
+    assert bench.parse().dump_outputs == str(tmp_path / "x")
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(Wl(0), str(a))
+    bench.dump_outputs(Wl(1), str(b))
+    names = sorted(os.listdir(a))
+    assert names == ["extra.npy", "loss.npy", "state.0.bias.npy", "state.0.weight.npy", "state.1.bias.npy",
+                     "state.1.running_mean.npy", "state.1.running_var.npy", "state.1.weight.npy"]   # (num_batches_tracked: int64)
+    assert names == sorted(os.listdir(b))
+    for n in names:
+        assert np.load(a / n).dtype == np.float32, n
+    assert np.load(a / "loss.npy").tolist() == [0.25] and np.load(b / "loss.npy").tolist() == [1.25]
+    w = Wl(0).model[0].weight.detach().reshape(-1)
+    assert w.numel() > bench.DUMP_SAMPLE and np.load(a / "state.0.weight.npy").shape == (bench.DUMP_SAMPLE,)
+    got = np.load(a / "state.0.weight.npy")
+    pos = [int(np.flatnonzero(w.numpy() == v)[0]) for v in got[:50]]       # the sampled positions, recovered from the values
+    got_b, w_b = np.load(b / "state.0.weight.npy"), Wl(1).model[0].weight.detach().reshape(-1).numpy()
+    assert np.array_equal(got_b[:50], w_b[pos])                              # the same positions for another model of that size
+    assert np.array_equal(np.load(a / "state.0.bias.npy"), Wl(0).model[0].bias.detach().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(Wl(0), str(tmp_path / "c"))
+    assert not (tmp_path / "c").exists()
+
+
+def test_run_workload_dumps_the_state_of_the_last_timed_step(tmp_path, monkeypatch):
+    """run_workload calls dump_outputs after exactly `steps` timed steps (after the warm-up, before the shader-clock and
+    kernel-timer passes run further steps), and on rank 0 only."""
+    import types
+    import numpy as np
+    import torch
+    from deeplearningexamples_amd import _cabi
+
+    class Counting:
+        name = "counting"
+
+        def __init__(self, args, rank, world, device):
+            self.model = torch.nn.Linear(4, 3)
+            self.n, self.loss, self.samples_per_step, self.scaling = 0, None, 8, "weak"
+
+        def step(self):
+            self.n += 1
+            with torch.no_grad():
+                self.model.weight.fill_(self.n)
+            self.loss = torch.tensor([float(self.n)])
+
+        def dtype_name(self):
+            return "fp32"
+
+        def config(self):
+            return {}
+
+    class NoTimer:
+        def report(self):
+            return []
+
+    monkeypatch.setitem(bench.WORKLOADS, "counting", Counting)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(_cabi, "KernelTimer", NoTimer)
+    monkeypatch.setattr(_cabi, "set_timer", lambda t: None)
+    monkeypatch.setenv("DLE_BENCH_SCLK", "1")
+    args = types.SimpleNamespace(no_kernel_timer=False, dump_outputs=str(tmp_path / "r0"))
+    rec = bench.run_workload("counting", args, 0, 1, "cpu", 5, 2)
+    assert rec["steps"] == 5 and rec["final_loss"] > 7                   # further steps ran after the timed ones
+    assert np.load(tmp_path / "r0" / "loss.npy").tolist() == [7.0]         # 2 warm-up + 5 timed
+    assert np.all(np.load(tmp_path / "r0" / "state.weight.npy") == 7.0)
+    args.dump_outputs = str(tmp_path / "r1")
+    assert bench.run_workload("counting", args, 1, 1, "cpu", 5, 2) is None
+    assert not (tmp_path / "r1").exists()

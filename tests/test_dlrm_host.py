@@ -94,7 +94,7 @@ def test_all_to_all_layout_two_ranks_gloo():
 
 
 def test_roc_auc_matches_sklearn_and_reference():
-    """dlrm/utils.roc_auc_score vs sklearn (the definition the reference restates) and, when the tree is mounted, vs the
+    """dlrm/utils.roc_auc_score vs sklearn (the definition the reference restates) and vs the stored results of the
     reference's own function (dlrm/scripts/utils.py:289-320): ties, skewed classes, one-class input."""
     import numpy as np
     import torch
@@ -109,17 +109,11 @@ def test_roc_auc_matches_sklearn_and_reference():
     for yt, ys in cases:
         assert abs(roc_auc_score(yt, ys) - sk_auc(yt.numpy(), ys.numpy())) < 1e-9
     assert np.isnan(roc_auc_score(torch.ones(10), torch.rand(10, generator=g)))
-    from oracle import _ref_import as R
-    if R.have_reference():
-        import importlib.util, os
-        spec = importlib.util.spec_from_file_location("ref_dlrm_utils_auc", os.path.join(
-            R.REF, "PyTorch/Recommendation/DLRM/dlrm/scripts/utils.py"))
-        src = open(spec.origin).read()
-        ns = {"torch": torch}
-        start = src.index("def roc_auc_score")
-        exec(compile(src[start:], spec.origin, "exec"), ns)                                # the function alone (the module imports dllogger)
-        for yt, ys in cases[:2]:
-            assert abs(roc_auc_score(yt, ys) - ns["roc_auc_score"](yt.clone(), ys.clone())) < 1e-6
+    # the reference's own function on the first two cases, stored by oracle/make_golden.py
+    ref = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_interfaces.json")))["dlrm_roc_auc"]
+    assert len(ref) == 2
+    for (yt, ys), r in zip(cases[:2], ref):
+        assert abs(roc_auc_score(yt, ys) - r) < 1e-6
 
 
 # ---- row-sharded placement (BASELINE.json configs[3] as worded; deeplearningexamples_amd/dlrm/row_sharded.py)
@@ -202,27 +196,15 @@ def test_row_sharded_exchange_two_ranks_gloo():
         assert ret[0] and ret[1]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/PyTorch"), reason="reference tree not mounted")
 def test_module_signatures_follow_the_reference_classes():
     """DistributedDlrm / DlrmBottom / DlrmTop (model/distributed.py:106-180, nn/parts.py:25-100): the reference's argument NAMES in
-    the reference's ORDER (extra, defaulted arguments may follow), read out of its sources."""
-    import ast
+    the reference's ORDER (extra, defaulted arguments may follow), read out of its sources into tests/golden/reference_interfaces.json."""
     import inspect
     from deeplearningexamples_amd.dlrm import model as M
-    root = "/root/reference/PyTorch/Recommendation/DLRM/dlrm/"
-
-    def ref_args(path, cls, fn):
-        for n in ast.walk(ast.parse(open(root + path).read())):
-            if isinstance(n, ast.ClassDef) and n.name == cls:
-                for f in n.body:
-                    if isinstance(f, ast.FunctionDef) and f.name == fn:
-                        return [a.arg for a in f.args.args[1:]]
-        raise AssertionError((path, cls, fn))
-
-    for path, cls, fn in (("model/distributed.py", "DistributedDlrm", "__init__"), ("model/distributed.py", "DistributedDlrm", "forward"),
-                          ("nn/parts.py", "DlrmBottom", "__init__"), ("nn/parts.py", "DlrmBottom", "forward"),
-                          ("nn/parts.py", "DlrmTop", "__init__")):
-        want = ref_args(path, cls, fn)
+    sigs = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_interfaces.json")))["dlrm_signatures"]
+    for cls, fn in (("DistributedDlrm", "__init__"), ("DistributedDlrm", "forward"), ("DlrmBottom", "__init__"), ("DlrmBottom", "forward"),
+                    ("DlrmTop", "__init__")):
+        want = sigs["%s.%s" % (cls, fn)]
         got = list(inspect.signature(getattr(getattr(M, cls), fn)).parameters)[1:]
         assert got[:len(want)] == want or (fn == "forward" and cls == "DlrmBottom" and got[:2] == want[:2]), (cls, fn, want, got)
     assert hasattr(M.DistributedDlrm, "from_dict")

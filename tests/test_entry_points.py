@@ -72,7 +72,6 @@ def test_reference_command_lines_parse():
     """The reference's own command lines (README / scripts) must not end in an argparse error: every flag of
     ConvNets/main.py:89-356, run_pretraining.py:140-321 and dlrm/scripts/main.py:43-143 is known to the drop-in parsers."""
     import argparse
-    import re
     from deeplearningexamples_amd.convnets.main import add_parser_arguments
     from deeplearningexamples_amd.bert.run_pretraining import parse_arguments
     from deeplearningexamples_amd.dlrm.main import parse_flags
@@ -96,38 +95,40 @@ def test_reference_command_lines_parse():
                      "/ck", "--load_checkpoint_path", "/ck", "--test_freq", "100", "--test_after", "0.5", "--auc_threshold",
                      "0.8025", "--test_batch_size", "131072", "--mode", "test", "--dataset_type", "parametric"])
     assert f.auc_threshold == 0.8025 and f.test_freq == 100 and f.save_checkpoint_path == "/ck" and f.mode == "test"
-    ref = "/root/reference/PyTorch"
-    if os.path.isdir(ref):          # every flag the reference defines is accepted here (flag NAMES; semantics: the GPU test below)
-        ours = {"rn50": add_parser_arguments(argparse.ArgumentParser())}
-        src = open(ref + "/Classification/ConvNets/main.py").read()
-        known = {o for act in ours["rn50"]._actions for o in act.option_strings}
-        missing = [x for x in set(re.findall(r'"(--[a-zA-Z0-9_-]+)"', src[src.index("def add_parser_arguments"):src.index("def prepare_for_training")])) if x not in known]
-        assert not missing, missing
-        src = open(ref + "/LanguageModeling/BERT/run_pretraining.py").read()
-        flags = set(re.findall(r"""add_argument\(\s*['"](--[a-zA-Z0-9_-]+)['"]""", src))
-        import deeplearningexamples_amd.bert.run_pretraining as bp
-        psrc = open(bp.__file__).read()
-        missing = [x for x in flags if '"%s"' % x not in psrc]
-        assert not missing, missing
-        src = open(ref + "/Recommendation/DLRM/dlrm/scripts/main.py").read()
-        flags = set(re.findall(r'DEFINE_[a-z]+\(\s*"([a-zA-Z0-9_]+)"', src))
-        import deeplearningexamples_amd.dlrm.main as dm
-        known = {o for act in dm.build_parser()._actions for o in act.option_strings}
-        missing = [x for x in flags if "--" + x not in known]
-        assert not missing and len(flags) >= 45, (missing, len(flags))
-        # absl gives every boolean flag a --no<name> twin (and shuffle_batch_order the short name --shuffle)
-        booleans = set(re.findall(r'DEFINE_boolean\(\s*"([a-zA-Z0-9_]+)"', src))
-        assert len(booleans) >= 10 and not [x for x in booleans if "--no" + x not in known] and "--shuffle" in known
-        # SpeechSynthesis/Tacotron2: train.py:45-160 + tacotron2/arg_parser.py:40-107 + waveglow/arg_parser.py:30-64
-        from deeplearningexamples_amd.tacotron2 import train as t2
-        from deeplearningexamples_amd.waveglow import train as wg
-        base = ref + "/SpeechSynthesis/Tacotron2/"
-        common = set(re.findall(r"""add_argument\(\s*(?:'-[a-z]+',\s*)?'(--[a-zA-Z0-9_-]+)'""", "\n".join(l for l in open(base + "train.py") if not l.lstrip().startswith("#"))))
-        for mod, extra in ((t2, "tacotron2/arg_parser.py"), (wg, "waveglow/arg_parser.py")):
-            flags = common | set(re.findall(r"""add_argument\(\s*'(--[a-zA-Z0-9_-]+)'""", open(base + extra).read()))
-            known = _known_flags(mod)
-            missing = sorted(x for x in flags if x not in known)
-            assert not missing and len(flags) > 50 - 10 * (mod is wg), (mod.__name__, missing, len(flags))
+    # every flag the reference defines is accepted here (flag NAMES; semantics: the GPU test below).  The reference's flag names are
+    # stored in tests/golden/reference_interfaces.json (oracle/make_golden.py reference_interfaces reads them out of its sources)
+    names = _reference_interfaces()["flag_names"]
+    ours = {"rn50": add_parser_arguments(argparse.ArgumentParser())}
+    known = {o for act in ours["rn50"]._actions for o in act.option_strings}
+    missing = [x for x in names["convnets"] if x not in known]
+    assert not missing, missing
+    import deeplearningexamples_amd.bert.run_pretraining as bp
+    psrc = open(bp.__file__).read()
+    missing = [x for x in names["bert"] if '"%s"' % x not in psrc]
+    assert not missing, missing
+    flags = names["dlrm"]
+    import deeplearningexamples_amd.dlrm.main as dm
+    known = {o for act in dm.build_parser()._actions for o in act.option_strings}
+    missing = [x for x in flags if "--" + x not in known]
+    assert not missing and len(flags) >= 45, (missing, len(flags))
+    # absl gives every boolean flag a --no<name> twin (and shuffle_batch_order the short name --shuffle)
+    booleans = names["dlrm_booleans"]
+    assert len(booleans) >= 10 and not [x for x in booleans if "--no" + x not in known] and "--shuffle" in known
+    # SpeechSynthesis/Tacotron2: train.py:45-160 + tacotron2/arg_parser.py:40-107 + waveglow/arg_parser.py:30-64
+    from deeplearningexamples_amd.tacotron2 import train as t2
+    from deeplearningexamples_amd.waveglow import train as wg
+    for mod, key in ((t2, "tacotron2"), (wg, "waveglow")):
+        flags = names[key]
+        known = _known_flags(mod)
+        missing = sorted(x for x in flags if x not in known)
+        assert not missing and len(flags) > 50 - 10 * (mod is wg), (mod.__name__, missing, len(flags))
+
+
+def _reference_interfaces():
+    """tests/golden/reference_interfaces.json; a keyword whose value is an expression in the reference's sources reads as Ellipsis."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    return json.load(open(os.path.join(here, "golden", "reference_interfaces.json")),
+                     object_hook=lambda d: {k: Ellipsis if v == "<expression>" else v for k, v in d.items()})
 
 
 def _known_flags(mod):
@@ -170,31 +171,13 @@ def _captured_parser(fn, argv):
     return seen["p"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/PyTorch"), reason="reference tree not mounted")
 def test_flag_defaults_choices_and_kinds_match_the_reference_sources():
-    """Same names is not yet a drop-in: every flag's DEFAULT, its choices and whether it is a switch are read out of the reference's
-    sources (ast over the add_argument / absl DEFINE_* calls of ConvNets/main.py, BERT/run_pretraining.py, Tacotron2/train.py +
-    arg_parser.py files, DLRM/dlrm/scripts/main.py) and compared with the parsers here.  The deviations are the ones listed."""
+    """Same names is not yet a drop-in: every flag's DEFAULT, its choices and whether it is a switch, as the reference's sources
+    define them (ast over the add_argument / absl DEFINE_* calls of ConvNets/main.py, BERT/run_pretraining.py, Tacotron2/train.py +
+    arg_parser.py files, DLRM/dlrm/scripts/main.py; stored in tests/golden/reference_interfaces.json by oracle/make_golden.py), are
+    compared with the parsers here.  The deviations are the ones listed."""
     import argparse
-    import ast
-    ref = "/root/reference/PyTorch"
-
-    def literal(node):
-        try:
-            return ast.literal_eval(node)
-        except Exception:
-            return Ellipsis                                   # an expression: not comparable
-
-    def argparse_flags(*paths):
-        out = {}
-        for path in paths:
-            for node in ast.walk(ast.parse(open(path).read())):
-                if isinstance(node, ast.Call) and getattr(node.func, "attr", None) == "add_argument":
-                    kw = {k.arg: literal(k.value) for k in node.keywords}
-                    for a in node.args:
-                        if isinstance(a, ast.Constant) and isinstance(a.value, str) and a.value.startswith("--"):
-                            out[a.value] = kw
-        return out
+    ref = _reference_interfaces()["flags"]
 
     def check(title, flags, parser, allowed):
         mine = {o: a for a in parser._actions for o in a.option_strings}
@@ -217,52 +200,46 @@ def test_flag_defaults_choices_and_kinds_match_the_reference_sources():
         return len(flags)
 
     from deeplearningexamples_amd.convnets.main import add_parser_arguments
-    n = check("convnets", argparse_flags(ref + "/Classification/ConvNets/main.py"), add_parser_arguments(argparse.ArgumentParser()),
+    n = check("convnets", ref["convnets"], add_parser_arguments(argparse.ArgumentParser()),
               # no DALI on ROCm: the synthetic loader is the default backend; 224 is what the reference fills in for resnet50 when
               # --image-size is None; "0" / 0
               {"--data-backend", "--image-size", "--gather-checkpoints"})
     assert n >= 40
     import deeplearningexamples_amd.bert.run_pretraining as bp
-    n = check("bert", argparse_flags(ref + "/LanguageModeling/BERT/run_pretraining.py"), _captured_parser(bp.parse_arguments, ["--bf16"]), set())
+    n = check("bert", ref["bert"], _captured_parser(bp.parse_arguments, ["--bf16"]), set())
     assert n >= 40
     from deeplearningexamples_amd.tacotron2 import train as t2
     from deeplearningexamples_amd.waveglow import train as wg
-    base = ref + "/SpeechSynthesis/Tacotron2/"
     argv = ["-o", "x", "-lr", "1", "--epochs", "1", "-bs", "1"]
-    for mod, extra in ((t2, "tacotron2/arg_parser.py"), (wg, "waveglow/arg_parser.py")):
+    for mod, key in ((t2, "tacotron2"), (wg, "waveglow")):
         # one entry point per model here: --model-name defaults to it (required, no default, in the reference's shared train.py)
-        n = check(mod.__name__, argparse_flags(base + "train.py", base + extra), _captured_parser(mod.parse_args, argv), {"--model-name"})
+        n = check(mod.__name__, ref[key], _captured_parser(mod.parse_args, argv), {"--model-name"})
         assert n >= 40
     # DLRM: absl DEFINE_<kind>(name, default, ...)
     from deeplearningexamples_amd.dlrm.main import build_parser
     mine = {o: a for a in build_parser()._actions for o in a.option_strings}
     bad, seen = [], 0
-    for node in ast.walk(ast.parse(open(ref + "/Recommendation/DLRM/dlrm/scripts/main.py").read())):
-        if isinstance(node, ast.Call) and getattr(node.func, "attr", "").startswith("DEFINE_"):
-            kind = node.func.attr[len("DEFINE_"):]
-            kw = {k.arg: literal(k.value) for k in node.keywords}
-            pos = [literal(a) for a in node.args]
-            name = pos[0] if pos else kw["name"]
-            default = kw["default"] if "default" in kw else pos[1]
-            a = mine.get("--" + name)
-            seen += 1
-            if a is None:
-                bad.append((name, "missing"))
-                continue
-            if kind == "list" and isinstance(default, str):
-                default = default.split(",")
-            if kind == "list" and default is not Ellipsis:
-                default = [int(x) for x in default]
-            if kind == "integer" and isinstance(default, str):
-                default = int(default)
-            if default is not Ellipsis and default != a.default:
-                bad.append((name, "default", default, a.default))
-            if kind == "enum":
-                ch = kw.get("enum_values", pos[2] if len(pos) > 2 else None)
-                if ch is not Ellipsis and list(ch) != list(a.choices):
-                    bad.append((name, "choices", ch, a.choices))
-            if kind == "boolean" and ("--no" + name not in mine or a.nargs != "?"):
-                bad.append((name, "not an absl boolean"))
+    for d in ref["dlrm"]:
+        kind, name, default = d["kind"], d["name"], d["default"]
+        a = mine.get("--" + name)
+        seen += 1
+        if a is None:
+            bad.append((name, "missing"))
+            continue
+        if kind == "list" and isinstance(default, str):
+            default = default.split(",")
+        if kind == "list" and default is not Ellipsis:
+            default = [int(x) for x in default]
+        if kind == "integer" and isinstance(default, str):
+            default = int(default)
+        if default is not Ellipsis and default != a.default:
+            bad.append((name, "default", default, a.default))
+        if kind == "enum":
+            ch = d["choices"]
+            if ch is not Ellipsis and list(ch) != list(a.choices):
+                bad.append((name, "choices", ch, a.choices))
+        if kind == "boolean" and ("--no" + name not in mine or a.nargs != "?"):
+            bad.append((name, "not an absl boolean"))
     assert not bad and seen >= 45, (bad, seen)
 
 
@@ -452,11 +429,8 @@ def test_entry_points_run_on_gpu(cuda, tmp_path):
 
 
 def test_bert_lr_schedule_matches_reference_scheduler():
-    """bert.engine.poly_warmup_lr == the oracle's restatement == (when the reference tree is present) the reference's
+    """bert.engine.poly_warmup_lr == the oracle's restatement == the stored learning rates of the reference's
     own PolyWarmUpScheduler stepped on a dummy optimizer (LanguageModeling/BERT/schedulers.py:109-136)."""
-    import os
-    import sys
-    import torch
     from deeplearningexamples_amd.bert.engine import poly_warmup_lr
     from oracle import bert_oracle as BO
     base, warm, total = 6e-3, 0.2843, 40
@@ -464,22 +438,11 @@ def test_bert_lr_schedule_matches_reference_scheduler():
     orc = [BO.poly_warmup_lr(s, base, warm, total) for s in range(1, total)]
     assert max(abs(a - b) for a, b in zip(ours, orc)) < 1e-12
     assert poly_warmup_lr(total + 5, base, warm, total) == 0.0
-    ref_dir = "/root/reference/PyTorch/LanguageModeling/BERT"
-    if os.path.isdir(ref_dir):
-        sys.path.insert(0, ref_dir)
-        try:
-            import schedulers as RS
-        finally:
-            sys.path.remove(ref_dir)
-        p = torch.nn.Parameter(torch.zeros(1))
-        opt = torch.optim.SGD([p], lr=base)
-        sch = RS.PolyWarmUpScheduler(opt, warmup=warm, total_steps=total, base_lr=base, device="cpu")
-        got = []
-        for k in range(0, 11):            # FusedLAMBAMP keeps the completed-step count in param_group["step"]
-            opt.param_groups[0]["step"] = torch.tensor(float(k))
-            sch.step()                    # run_pretraining.py:529 steps the scheduler BEFORE the optimizer
-            got.append(float(opt.param_groups[0]["lr"]))
-        assert max(abs(a - b) for a, b in zip(got, ours[:11])) < 1e-9
+    # the reference's PolyWarmUpScheduler stepped for k = 0..10 completed steps (run_pretraining.py:529 steps the scheduler BEFORE the
+    # optimizer; FusedLAMBAMP keeps the completed-step count in param_group["step"]), stored by oracle/make_golden.py
+    ref = _reference_interfaces()["bert_poly_warmup_lr"]
+    assert (ref["base_lr"], ref["warmup"], ref["total_steps"]) == (base, warm, total)
+    assert max(abs(a - b) for a, b in zip(ref["lr"], ours[:11])) < 1e-9 and len(ref["lr"]) == 11
 
 
 def test_flags_without_effect_are_reported_and_unknown_speech_flags_are_warned_about():

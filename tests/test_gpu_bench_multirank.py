@@ -59,19 +59,54 @@ def test_bench_two_ranks_survives_a_nested_failure_on_one_rank():
     assert d.get("note") == "nested phase timed out" or "injected" in r.stderr or "failed" in r.stderr
 
 
-def test_dlrm_bench_with_eight_ranks_places_the_bottom_mlp_alone_on_rank_zero():
-    """`bench.py --gpus 8 --workload dlrm`: the reference's get_device_mapping puts the bottom MLP on rank 0 WITHOUT tables when more
-    than four GPUs share the 26 tables (dlrm/utils/distributed.py:102-176; tests/golden/dlrm_placement.json) -- the configuration the
-    driver's 8-GPU scaling run executes, with ranks that own no numerical features and a rank that owns no embedding.  On a box with
-    fewer than eight GPUs the ranks share the devices and the exchange is staged through gloo (see the module docstring)."""
+def _free_port():
+    import socket
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
+
+
+def test_dlrm_bench_with_more_than_four_ranks_places_the_bottom_mlp_alone_on_rank_zero():
+    """`bench.py --gpus N --workload dlrm` with N > 4: the reference's get_device_mapping puts the bottom MLP on rank 0 WITHOUT tables
+    when more than four GPUs share the 26 tables (dlrm/utils/distributed.py:102-176; tests/golden/dlrm_placement.json) -- the
+    configuration the driver's 8-GPU scaling run executes, with ranks that own no numerical features and a rank that owns no embedding.
+
+    With >= 8 GPUs: `bench.py --gpus 8` (self-launch, RCCL).  With fewer, the ranks share the devices and the exchange is staged through
+    gloo (see the module docstring); the run then uses N = 5, the fewest ranks with this placement, and starts the ranks itself
+    (RANK / WORLD_SIZE / MASTER_* as torch.distributed.run sets them) -- the launcher's agent process opens the GPU too, and the 8
+    ranks + agent + this process (10) are more processes on one GPU than a shared test machine admits (6): 5 ranks + this process."""
+    from deeplearningexamples_amd.dlrm import placement as P
+    import bench
+    full = torch.cuda.device_count() >= 8
+    world = 8 if full else 5
+    mapping = P.get_device_mapping(bench.CRITEO_F15, world)
+    assert mapping["bottom_mlp"] == 0 and mapping["embedding"][0] == [] and all(mapping["embedding"][1:])
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    if torch.cuda.device_count() < 8:
-        env["DLE_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "dlrm", "--no-nested", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", "dlrm", "--no-nested", "--steps", "3",
            "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timer"]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-    assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-4000:])
+    if full:
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        out, err, rc = r.stdout, r.stderr, r.returncode
+    else:
+        import tempfile
+        env.update(DLE_BENCH_BACKEND="gloo", WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(_free_port()))
+        logs = [tempfile.TemporaryFile(mode="w+") for _ in range(world)]
+        procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(k), LOCAL_RANK=str(k)), stdout=logs[k], stderr=subprocess.STDOUT,
+                                  text=True, cwd=ROOT) for k in range(world)]
+        try:
+            rcs = [p.wait(timeout=600) for p in procs]
+        finally:
+            for p in procs:                              # one rank failed or hung: none may stay behind in its collectives
+                if p.poll() is None:
+                    p.kill()
+                    p.wait()
+        for f in logs:
+            f.seek(0)
+        texts = [f.read() for f in logs]
+        out, err, rc = texts[0], "\n".join(t[-1500:] for t in texts[1:]), max(rcs, key=abs)
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert rc == 0 and len(lines) == 1, (out[-2000:], err[-4000:])
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["comm"]["ranks_seen"] == 8 and d["value"] > 0
+    assert d["n_gpus"] == world and d["comm"]["ranks_seen"] == world and d["value"] > 0
     assert 0.6 < d["final_loss"] < 0.8                                   # random labels: ln 2, on every placement

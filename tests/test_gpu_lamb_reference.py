@@ -4,8 +4,9 @@ unmodified FusedLAMBAMP + PolyWarmUpScheduler + torch GradScaler, oracle/make_go
  * test_hip_kernels_through_reference_host_sequence -- always runs on the GPU box: the restated host sequence
    (oracle.lamb_oracle.FusedLambHost, itself bit-identical to the reference classes on CPU) with the two
    fused_lamb_CUDA entry points of shims/ (the b2 boundary, HIP kernels underneath) substituted for the numpy kernels.
- * test_reference_class_steps_on_hip_kernels -- when the reference tree is mounted: the reference's unmodified
-   FusedLAMBAMP class imported through shims/ steps CUDA tensors under torch.cuda.amp.GradScaler.
+ * test_reference_class_steps_on_hip_kernels -- the reference's unmodified FusedLAMBAMP class (the bytecode build() compiled
+   from the reference into oracle/_ref/, oracle/build_ref.py) imported through shims/ steps CUDA tensors under
+   torch.cuda.amp.GradScaler.
 Tolerance: fp32 arithmetic in a different association order (device pow / rsqrt vs numpy) -> 2e-5 relative on masters
 and moments after 6 steps; the fp16 model copies may differ by one fp16 ulp where a master sits on a rounding edge."""
 import os
@@ -21,6 +22,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "shims"))
 GOLD = os.path.join(ROOT, "tests", "golden", "lamb_ref_steps.npz")
+REF_BYTECODE = os.path.join(ROOT, "oracle", "_ref", "bert")        # oracle/build_ref.py, run by build()
 
 
 def _scaled_grads(case, g, scale, it):
@@ -86,11 +88,11 @@ def test_hip_kernels_through_reference_host_sequence(cuda):
     _check_against_gold(gold, case, host.p, host.m, host.v, host.p16)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/PyTorch/LanguageModeling/BERT/lamb_amp_opt"),
-                    reason="reference tree not mounted (GPU box): the unmodified class cannot be imported")
 def test_reference_class_steps_on_hip_kernels(cuda):
-    sys.path.insert(0, "/root/reference/PyTorch/LanguageModeling/BERT/lamb_amp_opt")
-    sys.path.insert(0, "/root/reference/PyTorch/LanguageModeling/BERT")
+    if not os.path.isfile(os.path.join(REF_BYTECODE, "lamb_amp_opt", "fused_lamb", "fused_lamb.pyc")):
+        pytest.fail("oracle/_ref/bert holds no compiled reference LAMB modules: run build() where the reference tree is present")
+    sys.path.insert(0, os.path.join(REF_BYTECODE, "lamb_amp_opt"))
+    sys.path.insert(0, REF_BYTECODE)
     from fused_lamb.fused_lamb import FusedLAMBAMP           # unmodified; imports apex / fused_lamb_CUDA from shims/
     import schedulers
     gold = np.load(GOLD)
@@ -129,7 +131,7 @@ def test_reference_class_steps_on_hip_kernels(cuda):
 
 
 def test_reference_class_call_trace_replayed_through_the_shims(cuda):
-    """The reference's unmodified FusedLAMBAMP.step CANNOT be imported on the GPU box (no reference tree there), so its calls travel
+    """Call for call, independently of the class run above: the reference's unmodified FusedLAMBAMP.step's calls travel
     as data: tests/golden/lamb_ref_trace.npz holds every call the class made into `fused_lamb_CUDA` over the golden scenario --
     the tensor lists and scalar arguments exactly as fused_lamb.py:147-258 passed them (7 optimizer steps incl. the overflow step:
     21 multi_tensor_l2norm + 28 multi_tensor_lamb calls) and what each call left behind (oracle/make_golden.py gen_lamb_trace,
