@@ -421,6 +421,8 @@ static int ln_bwd_launch(const void* dy, const void* z, const float* mean, const
   return 0;
 }
 
+// rows = 0 is refused, while the forward returns at once: the backward finishes column sums (dgamma / dbeta), and an empty
+// launch would leave them unwritten (accumulate = 0 promises they are overwritten).
 extern "C" int dle_layernorm_bwd(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
                                  void* dz, float* dgamma, float* dbeta, int64_t rows, int H, int accumulate,
                                  void* workspace, int64_t workspace_bytes, int dtype, hipStream_t stream) {
@@ -520,6 +522,7 @@ extern "C" int dle_embed_scatter_add(const void* dz, const int64_t* ids, float* 
 }
 
 // out[k][c] = sum over rows t with sel[t] == k of x[t][c], k in [0, K) (K small: token types).  Partials via workspace.
+// Rows whose sel lies outside [0, K) add to no output: they are dropped silently, not reported (token types are < K).
 template <int DT, int KMAX>
 __global__ __launch_bounds__(256) void rows_select_sum_kernel(const unsigned short* __restrict__ x,
                                                               const long long* __restrict__ sel, float* __restrict__ partial,

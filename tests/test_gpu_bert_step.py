@@ -307,3 +307,96 @@ def test_bert_large_24_layers_vs_reference(cuda, golden_dir, dtype):
     named = dict(model.named_parameters())
     r = gold["final_pooler_bias"]
     assert np.abs(named["bert.pooler.dense_act.bias"].detach().cpu().numpy() - r).max() <= 0.05 * np.abs(r).max() + 1e-4
+
+
+# ------------------------------------------------------------------ batched-GEMM attention path
+# bert/engine.py takes batched GEMMs + the softmax kernels (softmax_fwd_ / softmax_dropout_fwd_, softmax_bwd_ /
+# softmax_dropout_bwd_) when fused_attention is off or the shape is outside F.attention_supported.
+def _gradient_errors(tr, orc, bar):
+    """Relative L2 error of every gradient against the oracle's, the (name, error) pairs above `bar`."""
+    scale = float(tr.scaler.scale.item()) if tr.scaler.enabled else 1.0
+    bad = []
+    for n, p in orc.p.items():
+        g = tr.gview[n].reshape(-1).cpu().double() / scale
+        r = p.grad.reshape(-1).double()
+        if float(r.norm()) < 1e-6:
+            # key biases: the exact gradient is 0 (softmax is invariant to a per-row constant)
+            assert float(g.norm()) < 2e-2 * float(orc.p[n.replace("key.bias", "query.bias")].grad.norm()) + 1e-6, n
+            continue
+        rel = float((g - r).norm() / (r.norm() + 1e-12))
+        if rel > bar:
+            bad.append((n, round(rel, 4)))
+    return bad
+
+
+@pytest.mark.parametrize("dtype,bar", [(torch.float16, 0.03), (torch.bfloat16, 0.12)])
+def test_bert_batched_gemm_attention_gradients_vs_oracle(cuda, dtype, bar):
+    """The tiny config with fused attention switched off before the first forward: loss and first-step gradients against the
+    live oracle, at the bars of test_bert_first_step_gradients_vs_oracle (softmax_fwd_ / softmax_bwd_ end to end)."""
+    c = BO.BERT_STEP_CONFIG
+    state = BO.seeded_state(c["cfg"], c["seed"])
+    model, tr = _build(cuda, dtype, c, state)
+    tr.fused_attention = False
+    cpu_batch = BO.seeded_batch(c["cfg"], 99, 3)
+    orc = BO.BertOracle(c["cfg"], state)
+    lo = orc.loss(*cpu_batch)
+    lo.backward()
+    floor = abs(float(BO.BertOracle(c["cfg"], state, storage_dtype=dtype).loss(*cpu_batch)) - float(lo))
+    loss, dlog, dnsp = tr.forward(*[t.to(cuda) for t in cpu_batch])
+    assert not tr._sv["fused_attn"]
+    assert abs(loss.item() - float(lo)) <= 1e-3 * float(lo) + floor, (loss.item(), float(lo), floor)
+    tr.backward(dlog, dnsp)
+    torch.cuda.synchronize()
+    bad = _gradient_errors(tr, orc, bar)
+    assert not bad, bad[:12]
+
+
+@pytest.mark.parametrize("dtype,bar", [(torch.float16, 0.03), (torch.bfloat16, 0.12)])
+def test_bert_batched_gemm_attention_training_mode_vs_oracle(cuda, dtype, bar):
+    """Training mode (hidden / attention dropout 0.1) on the batched-GEMM path: the oracle runs under the kernels' keep masks
+    (softmax_dropout_fwd_ / softmax_dropout_bwd_ end to end)."""
+    c = BO.BERT_STEP_CONFIG
+    cfg = c["cfg"]
+    state = BO.seeded_state(cfg, c["seed"])
+    model, tr = _build(cuda, dtype, c, state, 0.1, 0.1)
+    tr.fused_attention = False
+    tr.keep_activations = True
+    cpu_batch = BO.seeded_batch(cfg, 99, 3)
+    b, s = cpu_batch[0].shape
+    loss, dlog, dnsp = tr.forward(*[t.to(cuda) for t in cpu_batch])
+    assert not tr._sv["fused_attn"]
+    tr.backward(dlog, dnsp)
+    torch.cuda.synchronize()
+    masks = _masks_from(tr, cfg, b, s)
+    keep = float(masks["attn0"].float().mean())
+    assert abs(keep - 0.9) < 5e-3, keep
+    orc = BO.BertOracle(cfg, state)
+    lo = orc.loss(*cpu_batch, masks=masks, p_hidden=0.1, p_attn=0.1)
+    lo.backward()
+    floor = abs(float(BO.BertOracle(cfg, state, storage_dtype=dtype).loss(*cpu_batch, masks=masks, p_hidden=0.1, p_attn=0.1)) - float(lo))
+    assert abs(loss.item() - float(lo)) <= 1e-3 * float(lo) + floor, (loss.item(), float(lo), floor)
+    bad = _gradient_errors(tr, orc, bar)
+    assert not bad, bad[:12]
+
+
+@pytest.mark.parametrize("dtype,bar", [(torch.float16, 0.03), (torch.bfloat16, 0.12)])
+def test_bert_seq64_outside_fused_envelope_vs_oracle(cuda, dtype, bar):
+    """S = 64 lies outside the fused attention kernels' envelope (S = 128 or a multiple of 128): the engine must take the
+    batched-GEMM + softmax path by itself.  Loss and every first-step gradient vs the CPU oracle."""
+    c = BO.BERT_STEP_CONFIG
+    cfg = dict(c["cfg"], seq=64)
+    state = BO.seeded_state(cfg, c["seed"])
+    model, tr = _build(cuda, dtype, dict(c, cfg=cfg), state)
+    cpu_batch = BO.seeded_batch(cfg, 7, 4)
+    assert cpu_batch[0].shape == (4, 64)
+    orc = BO.BertOracle(cfg, state)
+    lo = orc.loss(*cpu_batch)
+    lo.backward()
+    floor = abs(float(BO.BertOracle(cfg, state, storage_dtype=dtype).loss(*cpu_batch)) - float(lo))
+    loss, dlog, dnsp = tr.forward(*[t.to(cuda) for t in cpu_batch])
+    assert not tr._sv["fused_attn"]
+    assert abs(loss.item() - float(lo)) <= 1e-3 * float(lo) + floor, (loss.item(), float(lo), floor)
+    tr.backward(dlog, dnsp)
+    torch.cuda.synchronize()
+    bad = _gradient_errors(tr, orc, bar)
+    assert not bad, bad[:12]
