@@ -1,15 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: training samples/sec of the hot-path train step on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dlrm|rn50|bert]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dlrm|rn50|bert] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task statement): whole-job samples/sec over exactly K
-steps bracketed by barrier + device sync, max over ranks; plus
+steps bracketed by barrier + device sync, max over ranks.  A plain run does nothing else: it sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line.  With --full it also measures
   "roofline":     dominant kernel of the step, HIP-event timed inside the timed region, vs the MI355X peak
   "cpu_baseline": the CPU oracle (oracle/, a port of the reference's PyTorch-CPU path) timed on the host
-                  cores on a bounded sample, rank 0 at N=1 only.
+                  cores on a bounded sample, rank 0 at N=1 only
+  "workloads":    the other workloads of BASELINE.json's metric, each timed after the headline one.
 Inputs are synthetic, generated once and resident in HBM before the timed region (the reference's own
 synthetic loaders do the same: DLRM dlrm/data/datasets.py:32-61, RN50 dataloaders.py:520-549).
 """
@@ -42,11 +44,14 @@ def parse():
                     choices=["dlrm", "rn50", "bert", "bert_acc32", "waveglow", "tacotron2"])
     ap.add_argument("--batch", type=int, default=None, help="global batch (DLRM) / per-GPU batch (RN50, BERT)")
     ap.add_argument("--dtype", default=None, choices=[None, "fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baselines, the shader clock, the per-kernel roofline pass, "
+                         "the other workloads and the detail file (off: only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="with --full: no per-kernel roofline pass")
     ap.add_argument("--max-table-size", type=int, default=None)
     ap.add_argument("--no-nested", action="store_true",
-                    help="only the headline workload (default: the other workloads of BASELINE.json's "
+                    help="with --full: only the headline workload (default: the other workloads of BASELINE.json's "
                          "metric run after it and are reported under \"workloads\")")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline workload's last timed step computed (its loss and "
@@ -789,9 +794,10 @@ def dump_outputs(wl, d):
         np.save(os.path.join(d, k + ".npy"), a)
 
 
-def run_workload(name, args, rank, world, device, steps, warmup):
+def run_workload(name, args, rank, world, device, steps, warmup, full=True):
     """Build the workload, warm up, time exactly `steps` steps (barrier + synchronize on both sides, nothing else
-    inside), then the instrumented pass for the roofline.  Returns the record of this workload (rank 0) or None."""
+    inside), then, when `full`, the shader-clock and instrumented passes for the roofline.  Returns the record of this
+    workload (rank 0) or None."""
     from deeplearningexamples_amd import _cabi
     inject = os.environ.get("DLE_BENCH_FAIL_NESTED", "")           # "<workload>:<rank>": tests of the nested-failure path
     if inject and inject.split(":")[0] == name and int(inject.split(":")[1]) == rank:
@@ -814,12 +820,12 @@ def run_workload(name, args, rank, world, device, steps, warmup):
     if getattr(args, "dump_outputs", None) and rank == 0:
         dump_outputs(wl, args.dump_outputs)
     sclk = None
-    if os.environ.get("DLE_BENCH_SCLK", "1") == "1":
+    if full and os.environ.get("DLE_BENCH_SCLK", "1") == "1":
         sclk = sample_shader_clock(wl, max(2, min(steps, 10)), sample=rank == 0)
     # the same K steps again with a HIP-event pair around every C-ABI launch (on the launch stream) for the per-kernel
     # durations behind "roofline"; kept out of the region above (the event pairs inflate the step); every rank runs it
     timer = None
-    if not args.no_kernel_timer:
+    if full and not args.no_kernel_timer:
         timer = _cabi.KernelTimer()
         # per-kernel durations are taken with every kernel ALONE on the chip: the engines' second streams (weight gradients,
         # downsample branch, embedding update) are folded into one stream for this pass only -- side by side a kernel's event
@@ -945,7 +951,7 @@ def main():
     _cabi.lib()                                        # fail loudly if the HIP library is missing
     comm_rec = comm_info()                             # (a collective: every rank, before anything can diverge)
     nested_names = []
-    if not args.no_nested:
+    if args.full and not args.no_nested:
         # every workload BASELINE.json's metric / configs name, at every N: `bench.py --gpus N` yields the 1/2/4/8 curve of
         # BERT-L and DLRM too (nested records), not only of the headline workload
         nested_names = [w for w in ("waveglow", "tacotron2") if w != args.workload] \
@@ -960,7 +966,7 @@ def main():
     # ---- CPU leg first (rank 0, N = 1): the oracle on the host cores, bounded samples (>= 3 timed steps each); the GPU legs
     # then run back to back to the end of the process
     cpu = {}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         for w in [args.workload] + nested_names:
             try:
                 cpu[w] = WORKLOADS[w].cpu_baseline(None)
@@ -968,7 +974,7 @@ def main():
                 if w == args.workload:
                     raise
                 print("cpu baseline of %s failed: %r" % (w, e), file=sys.stderr)
-    rec = run_workload(args.workload, args, rank, world, device, args.steps, args.warmup)
+    rec = run_workload(args.workload, args, rank, world, device, args.steps, args.warmup, full=args.full)
     nested = {}
     printed = []
 
@@ -1000,8 +1006,9 @@ def main():
         w[args.workload] = compact(args.workload, rec, cpu.get(args.workload))
         order = [n for n in ("waveglow", "tacotron2", "bert_acc32", "dlrm", "bert", "rn50") if n in w]
         out["workloads"] = {n: w[n] for n in order}
-        write_detail({"headline": dict(rec, workload=args.workload, cpu_baseline=cpu.get(args.workload)),
-                      "nested": nested, "n_gpus": world})
+        if args.full:
+            write_detail({"headline": dict(rec, workload=args.workload, cpu_baseline=cpu.get(args.workload)),
+                          "nested": nested, "n_gpus": world})
         print(json.dumps(out), flush=True)
 
     import copy

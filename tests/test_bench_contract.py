@@ -212,3 +212,82 @@ def test_run_workload_dumps_the_state_of_the_last_timed_step(tmp_path, monkeypat
     args.dump_outputs = str(tmp_path / "r1")
     assert bench.run_workload("counting", args, 1, 1, "cpu", 5, 2) is None
     assert not (tmp_path / "r1").exists()
+    # a plain run (no --full): no step after the timed ones, no kernel timer, no roofline
+    monkeypatch.setattr(_cabi, "KernelTimer", None)
+    args.dump_outputs = str(tmp_path / "r2")
+    rec = bench.run_workload("counting", args, 0, 1, "cpu", 5, 2, full=False)
+    assert rec["final_loss"] == 7.0 and rec["roofline"] is None and rec["kernel_breakdown"] == []
+    assert np.load(tmp_path / "r2" / "loss.npy").tolist() == [7.0]
+
+
+def test_plain_run_does_only_what_the_headline_figure_needs(tmp_path, monkeypatch, capsys):
+    """`bench.py --steps K --warmup W` builds the headline workload alone, runs W + K steps and prints the line; the CPU
+    baselines, the nested workloads, the passes after the timed steps and the detail file come with --full only."""
+    import torch
+    import __graft_entry__
+    from deeplearningexamples_amd import _cabi
+
+    built, baselines, detail = [], [], []
+
+    def fake(wl_name):
+        class Fake:
+            name = wl_name
+
+            def __init__(self, args, rank, world, device):
+                built.append(wl_name)
+                self.model = torch.nn.Linear(4, 3)
+                self.n, self.loss, self.samples_per_step, self.scaling = 0, None, 8, "weak"
+
+            def step(self):
+                self.n += 1
+                self.loss = torch.tensor([float(self.n)])
+
+            def dtype_name(self):
+                return "bf16"
+
+            def config(self):
+                return {}
+
+            def cpu_baseline(self):
+                baselines.append(wl_name)
+                return {"value": 1.0, "cores": 1, "kind": "port", "steps": 3}
+        return Fake
+
+    class NoTimer:
+        def report(self):
+            return []
+
+    for w in bench.WORKLOADS:
+        monkeypatch.setitem(bench.WORKLOADS, w, fake(w))
+    monkeypatch.setattr(bench, "init_dist", lambda n: (0, 1, "cpu"))
+    monkeypatch.setattr(bench, "write_detail", detail.append)
+    monkeypatch.setattr(__graft_entry__, "build_product", lambda force=False: None)
+    monkeypatch.setattr(_cabi, "lib", lambda: None)
+    monkeypatch.setattr(_cabi, "KernelTimer", NoTimer)
+    monkeypatch.setattr(_cabi, "set_timer", lambda t: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setenv("DLE_BENCH_SCLK", "1")
+    for k in ("DLE_BENCH_WORKLOAD", "DLE_BENCH_NESTED", "DLE_BENCH_NESTED_STEPS", "DLE_BENCH_FAIL_NESTED"):
+        monkeypatch.delenv(k, raising=False)
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "d")])
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"], d["steps"], d["warmup"]) == \
+        ("training samples/sec", "samples/s", True, "bf16", 3, 2)
+    assert d["final_loss"] == 5.0 and d["ms_per_step"] > 0 and d["value"] > 0          # 2 warm-up + 3 timed steps, nothing after
+    assert os.path.exists(tmp_path / "d" / "loss.npy")
+    assert built == ["rn50"] and baselines == [] and detail == []
+    assert d["roofline"] is None and "cpu_baseline" not in d and list(d["workloads"]) == ["rn50"]
+
+    built.clear()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--full"])
+    monkeypatch.setenv("DLE_BENCH_NESTED_STEPS", "2,1")
+    bench.main()
+    d = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
+    assert d["final_loss"] > 5.0                                         # the shader-clock / kernel-timer passes ran further steps
+    assert built[0] == "rn50" and sorted(built) == sorted(bench.WORKLOADS) and sorted(baselines) == sorted(bench.WORKLOADS)
+    assert len(detail) == 1 and "cpu_baseline" in d
+    assert list(d["workloads"]) == ["waveglow", "tacotron2", "bert_acc32", "dlrm", "bert", "rn50"]

@@ -23,7 +23,8 @@ def _bench(extra_env, timeout=900):
     if torch.cuda.device_count() < 2:
         env["DLE_BENCH_BACKEND"] = "gloo"
     env.update(extra_env)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, lines

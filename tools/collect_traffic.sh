@@ -6,7 +6,7 @@ cd $R
 echo "{" > gpurun_out/traffic_new.json
 first=1
 for w in "${@:-rn50}"; do
-  key=$(python bench.py --workload $w --no-nested --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['roofline']['heaviest_shape'])")
+  key=$(python bench.py --full --workload $w --no-nested --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['roofline']['heaviest_shape'])")
   rec=$(tools/pmc_traffic.sh $w "$key")
   [ $first -eq 1 ] || echo "," >> gpurun_out/traffic_new.json
   first=0
