@@ -51,6 +51,11 @@ _SIGS = {
     "dle_emb_sgd_workspace_bytes": (c_i64, [c_void_p, c_int, c_int, c_i64]),
     "dle_emb_onehot_try": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_i64, c_int, c_int, c_i64, c_int, c_void_p, c_i64, c_void_p]),
+    "dle_emb_onehot_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int,
+                                        c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    "dle_emb_adam_workspace_bytes": (c_i64, [c_void_p, c_int, c_int, c_i64]),
+    "dle_emb_adam_dedup_ws": (c_int, [c_void_p] * 9 + [c_float, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_i64,
+                                      c_int, c_int, c_i64, c_int, c_void_p, c_i64, c_void_p]),
     "dle_cast_rows": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_int, c_void_p]),
     "dle_bce_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "dle_conv1x1_bnbwd_dgrad": (c_int, [c_void_p] * 16 + [c_i64, c_int, c_int, c_int, c_int, c_void_p]),
@@ -170,6 +175,8 @@ _SIGS = {
                            c_float, c_float, c_int, c_int, c_void_p, c_int, c_void_p]),
     "dle_mt_adam": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                             c_float, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    "dle_mt_adam_copy": (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "dle_wg_taps": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_i64, c_int, c_void_p]),
     "dle_wg_taps_bwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_i64, c_i64, c_int, c_void_p]),
     "dle_wg_gate_fwd": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p]),
@@ -274,7 +281,7 @@ class KernelTimer:
 
     # entry points whose duration depends on state they consume (row lists, touched-row sets): never replayed
     # (the optimizer updates are not pure either: a replay would step the weights / moments again)
-    _STATEFUL = ("emb_sgd", "emb_sparse", "emb_link", "emb_grad", "amp_update", "mt_lamb", "mt_sgd", "mt_adam")
+    _STATEFUL = ("emb_sgd", "emb_adam", "emb_sparse", "emb_link", "emb_grad", "amp_update", "mt_lamb", "mt_sgd", "mt_adam")
 
     def replay(self, name, tag, iters=20, warmup=3, cold=False):
         """Average duration (ms) of the recorded call re-launched back to back: ONE event pair around `iters`

@@ -213,6 +213,41 @@ extern "C" int64_t dle_emb_onehot_workspace_bytes(int n_tables, int64_t batch) {
   return (int64_t)n_tables * oh_slices(n_tables, batch) * OH_ROWS * OH_D * 4;
 }
 
+// the kernel's envelope (16-bit gradients, 16-byte aligned rows, 32-bit buffer offsets, <= 64 tables of <= 128 rows): fills p
+static bool oh_envelope(OhArgs& p, float* weight, const int64_t* rows, const void* grad, const float* lr_dev, float lr_host,
+                        const float* scale_dev, const float* skip_flag_dev, const int* tab_t, const int64_t* tab_base,
+                        const int* tab_rows, int n_tab, int64_t batch, int tables, int64_t grad_batch_stride, int grad_dtype,
+                        void* ws, int64_t ws_bytes) {
+  if (grad_dtype != DLE_F16 && grad_dtype != DLE_BF16) return false;
+  if ((grad_batch_stride % 8) != 0 || ((((uintptr_t)grad) | ((uintptr_t)ws)) & 15) != 0) return false;
+  if (batch * grad_batch_stride * 2 >= 0xFFFFFFE0LL || batch < OH_TG) return false;
+  p.weight = weight; p.rows = (const long long*)rows; p.grad = (const unsigned short*)grad; p.lr_dev = lr_dev; p.lr_host = lr_host;
+  p.scale = scale_dev; p.skip = skip_flag_dev; p.ws = (float*)ws; p.batch = batch; p.gstride = grad_batch_stride; p.T = tables;
+  p.n = n_tab; p.slices = oh_slices(n_tab, batch);
+  if (ws_bytes < dle_emb_onehot_workspace_bytes(n_tab, batch)) return false;
+  for (int i = 0; i < n_tab; ++i) {
+    if (tab_rows[i] > OH_ROWS || tab_rows[i] > 255) return false;
+    p.t[i] = tab_t[i]; p.base[i] = tab_base[i]; p.nrows[i] = tab_rows[i];
+  }
+  return true;
+}
+
+// the segment-sum kernel alone: partial blocks ws[k][slice][row < nrows[k]][128]; 0 or a launch error + 1000
+static int oh_launch_partials(const OhArgs& p, int grad_dtype, hipStream_t stream) {
+  const size_t lds = 64 * 1024;                                          // 2 x 16 KiB tiles + ids; the meeting buffer of the halves
+#define GO(DT)                                                                                                           \
+  do {                                                                                                                   \
+    static bool attr_set = false;                                                                                        \
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)emb_onehot_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
+    hipLaunchKernelGGL((emb_onehot_kernel<DT>), dim3(p.n * p.slices), dim3(512), lds, stream, p);                        \
+  } while (0)
+  if (grad_dtype == DLE_F16) GO(DLE_F16); else GO(DLE_BF16);
+#undef GO
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { dle_set_error("emb_onehot launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
+  return 0;
+}
+
 // 1: launched; 0: outside the envelope (the caller keeps its register / LDS forms); > 1: error.
 extern "C" int dle_emb_onehot_try(float* weight, const int64_t* rows, const void* grad, const float* lr_dev, float lr_host,
                                   const float* scale_dev, const float* skip_flag_dev, const int* tab_t, const int64_t* tab_base,
@@ -226,31 +261,32 @@ extern "C" int dle_emb_onehot_try(float* weight, const int64_t* rows, const void
   // this launch (dle_check_nonfinite runs on the gradient first) and arrives here as skip_flag_dev, which drops the whole step.
   // A caller without a scaler (bf16, skip_flag_dev == NULL) gets a poisoned table instead of a poisoned row from a non-finite
   // gradient -- the run is lost either way; DLE_EMB_ONEHOT=0 keeps the row-local forms.
-  if (grad_dtype != DLE_F16 && grad_dtype != DLE_BF16) return 0;
-  if ((grad_batch_stride % 8) != 0 || ((((uintptr_t)grad) | ((uintptr_t)ws)) & 15) != 0) return 0;
-  if (batch * grad_batch_stride * 2 >= 0xFFFFFFE0LL || batch < OH_TG) return 0;
   OhArgs p;
-  p.weight = weight; p.rows = (const long long*)rows; p.grad = (const unsigned short*)grad; p.lr_dev = lr_dev; p.lr_host = lr_host;
-  p.scale = scale_dev; p.skip = skip_flag_dev; p.ws = (float*)ws; p.batch = batch; p.gstride = grad_batch_stride; p.T = tables;
-  p.n = n_tab; p.slices = oh_slices(n_tab, batch);
-  if (ws_bytes < dle_emb_onehot_workspace_bytes(n_tab, batch)) return 0;
-  for (int i = 0; i < n_tab; ++i) {
-    if (tab_rows[i] > OH_ROWS || tab_rows[i] > 255) return 0;
-    p.t[i] = tab_t[i]; p.base[i] = tab_base[i]; p.nrows[i] = tab_rows[i];
-  }
-  const size_t lds = 64 * 1024;                                          // 2 x 16 KiB tiles + ids; the meeting buffer of the halves
-#define GO(DT)                                                                                                           \
-  do {                                                                                                                   \
-    static bool attr_set = false;                                                                                        \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)emb_onehot_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
-    hipLaunchKernelGGL((emb_onehot_kernel<DT>), dim3(n_tab * p.slices), dim3(512), lds, stream, p);                      \
-  } while (0)
-  if (grad_dtype == DLE_F16) GO(DLE_F16); else GO(DLE_BF16);
-#undef GO
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { dle_set_error("emb_onehot launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
+  if (!oh_envelope(p, weight, rows, grad, lr_dev, lr_host, scale_dev, skip_flag_dev, tab_t, tab_base, tab_rows, n_tab, batch, tables,
+                   grad_batch_stride, grad_dtype, ws, ws_bytes))
+    return 0;
+  const int rc = oh_launch_partials(p, grad_dtype, stream);
+  if (rc) return rc;
   hipLaunchKernelGGL(emb_onehot_fold_kernel, dim3(n_tab * OH_ROWS), dim3(128), 0, stream, p);
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { dle_set_error("emb_onehot fold launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
+  return 1;
+}
+
+// The segment sums alone (the sparse Adam update of emb_adam.hip folds them itself): fp32 partial blocks
+// ws[k][slice][r][128] for r < tab_rows[k], nothing else is written; *slices_out = the slice count.  dim must be 128.
+// 1: launched; 0: outside the envelope; > 1: error.
+extern "C" int dle_emb_onehot_partials(const int64_t* rows, const void* grad, const float* skip_flag_dev, const int* tab_t,
+                                       const int64_t* tab_base, const int* tab_rows, int n_tab, int64_t batch, int tables, int dim,
+                                       int64_t grad_batch_stride, int grad_dtype, void* ws, int64_t ws_bytes, int* slices_out,
+                                       hipStream_t stream) {
+  if (n_tab <= 0 || n_tab > 64 || dim != OH_D || !ws || !slices_out) return 0;
+  OhArgs p;
+  if (!oh_envelope(p, nullptr, rows, grad, nullptr, 0.f, nullptr, skip_flag_dev, tab_t, tab_base, tab_rows, n_tab, batch, tables,
+                   grad_batch_stride, grad_dtype, ws, ws_bytes))
+    return 0;
+  const int rc = oh_launch_partials(p, grad_dtype, stream);
+  if (rc) return rc;
+  *slices_out = p.slices;
   return 1;
 }

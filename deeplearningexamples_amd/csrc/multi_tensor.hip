@@ -457,6 +457,83 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_adam(const long long* __restrict_
   }
 }
 
+// -------------------------------------------------------------------- Adam with the 16-bit working-copy refresh (apex FusedAdam)
+// DLRM --Adam_MLP_optimizer (Recommendation/DLRM/dlrm/scripts/main.py:468-471): apex FusedAdam with bias_correction, weight_decay 0,
+// behind GradScaler.step (found_inf skips the step and t does not advance).  lists: g (fp32, scaled by the loss scale), p, exp_avg,
+// exp_avg_sq (fp32), and a same-shape 16-bit copy of p (pointer 0: a tensor without one) rewritten from the updated master in the
+// same pass, as mt_sgd does with model_copy.  grad = g * inv_scale * tensor_mul[tensor] (tensor_mul: per-tensor multiplier, the
+// 1 / world of the reference's scale_MLP_gradients on the bottom MLP, main.py:720-723; NULL: 1), then FusedAdam's math:
+//   m = b1 m + (1 - b1) grad;  v = b2 v + (1 - b2) grad^2;  p -= lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps).
+template <int CT>
+__global__ __launch_bounds__(MT_BLOCK) void mt_adam_copy(const long long* __restrict__ table, int n, int chunk,
+                                                         const float* __restrict__ skip_flag, const float* __restrict__ lr_ptr,
+                                                         float lr_host, float beta1, float beta2, float eps,
+                                                         const int* __restrict__ step_ptr, const float* __restrict__ inv_scale,
+                                                         const float* __restrict__ tensor_mul) {
+  if (skip_flag && *skip_flag != 0.f) return;   // GradScaler found_inf -> the step is skipped
+  const MtTable t = mt_view(table, n);
+  const long long c = blockIdx.x;
+  const int ti = mt_find(t, c);
+  const long long off = (c - t.chunk_start[ti]) * chunk;
+  long long len = t.size[ti] - off;
+  if (len > chunk) len = chunk;
+  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  const float gs = (inv_scale ? *inv_scale : 1.0f) * (tensor_mul ? tensor_mul[ti] : 1.0f);
+  const int step = *step_ptr;
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
+  const float* g = (const float*)t.ptr[0 * n + ti] + off;
+  float* p = (float*)t.ptr[1 * n + ti] + off;
+  float* m = (float*)t.ptr[2 * n + ti] + off;
+  float* v = (float*)t.ptr[3 * n + ti] + off;
+  unsigned short* pc0 = CT >= 0 ? (unsigned short*)t.ptr[4 * n + ti] : nullptr;
+  const bool has_pc = CT >= 0 && pc0 != nullptr;
+  unsigned short* pc = has_pc ? pc0 + off : nullptr;
+  const bool vec = ((((uintptr_t)g) | ((uintptr_t)p) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0 && ((((uintptr_t)pc) & 7) == 0);
+  const long long len4 = len & ~3LL;
+  for (long long i = (long long)threadIdx.x * 4; i < len; i += MT_BLOCK * 4) {
+    const bool full = i < len4;
+    const int cnt = full ? 4 : (int)(len - i);
+    float4_t rg, rp, rm, rv;
+    if (full) {
+      rg = ld4<DLE_F32>(g + i, vec);
+      rp = ld4<DLE_F32>(p + i, vec);
+      rm = ld4<DLE_F32>(m + i, vec);
+      rv = ld4<DLE_F32>(v + i, vec);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const bool ok = k < cnt;
+        rg[k] = ok ? g[i + k] : 0.f;
+        rp[k] = ok ? p[i + k] : 0.f;
+        rm[k] = ok ? m[i + k] : 0.f;
+        rv[k] = ok ? v[i + k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gr = rg[k] * gs;
+      rm[k] = beta1 * rm[k] + (1.f - beta1) * gr;
+      rv[k] = beta2 * rv[k] + (1.f - beta2) * gr * gr;
+      const float denom = sqrtf(rv[k] / bc2) + eps;
+      rp[k] = rp[k] - lr * ((rm[k] / bc1) / denom);
+    }
+    if (full) {
+      st4<DLE_F32>(p + i, rp, vec);
+      st4<DLE_F32>(m + i, rm, vec);
+      st4<DLE_F32>(v + i, rv, vec);
+      if (has_pc) st4<(CT >= 0 ? CT : DLE_F16)>(pc + i, rp, vec);
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        p[i + k] = rp[k];
+        m[i + k] = rm[k];
+        v[i + k] = rv[k];
+        if (has_pc) MtIO<(CT >= 0 ? CT : DLE_F16)>::st(pc + i + k, rp[k]);
+      }
+    }
+  }
+}
+
 // param_norm[t] / update_norm[t] = sqrt of tensor t's chunk partials (the fold of mt_l2norm_finish, both arrays in one launch)
 __global__ __launch_bounds__(MT_BLOCK) void mt_lamb_norms_finish(const float* __restrict__ partial_p, const float* __restrict__ partial_u,
                                                                  const long long* __restrict__ table, int n,
@@ -621,6 +698,22 @@ extern "C" int dle_mt_adam(const int64_t* table_dev, int n_tensors, int64_t tota
   hipLaunchKernelGGL(mt_adam, dim3((unsigned)total_chunks), dim3(MT_BLOCK), 0, stream, (const long long*)table_dev, n_tensors,
                      chunk, skip_flag_dev, lr_dev, lr_host, beta1, beta2, eps, weight_decay, step_dev, inv_scale_dev,
                      grad_norm_dev, max_grad_norm);
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, int copy_dtype,
+                                const float* skip_flag_dev, const float* lr_dev, float lr_host, float beta1, float beta2, float eps,
+                                const int* step_dev, const float* inv_scale_dev, const float* tensor_mul_dev, hipStream_t stream) {
+  DLE_CHECK_ARG(table_dev && step_dev, "mt_adam_copy: null table / step");
+  DLE_CHECK_ARG(copy_dtype == -1 || copy_dtype == DLE_F16 || copy_dtype == DLE_BF16, "mt_adam_copy: bad copy dtype %d", copy_dtype);
+  if (n_tensors == 0 || total_chunks == 0) return 0;
+  dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
+#define GO(CT) hipLaunchKernelGGL(mt_adam_copy<CT>, grid, block, 0, stream, (const long long*)table_dev, n_tensors, chunk, skip_flag_dev, lr_dev, lr_host, beta1, beta2, eps, step_dev, inv_scale_dev, tensor_mul_dev)
+  if (copy_dtype == DLE_F16) GO(DLE_F16);
+  else if (copy_dtype == DLE_BF16) GO(DLE_BF16);
+  else GO(-1);
+#undef GO
   DLE_LAUNCH_CHECK();
   return 0;
 }

@@ -4,7 +4,11 @@ Mirrors the reference's step (Recommendation/DLRM/dlrm/scripts/main.py):
     forward_backward  :585-594   autocast forward, BCEWithLogits on this rank's label slice, scaled backward
     weight_update     :596-608   scaler.step(mlp_optimizer); scaler.unscale_(embedding_optimizer);
                                  embedding_optimizer.step(); scaler.update()
-    LR compensation   :444-452   model-parallel parts (embeddings, bottom MLP) use lr / world_size
+    LR compensation   :444-452   model-parallel parts (embeddings, bottom MLP) use lr / world_size under SGD; under Adam
+                                 (--Adam_embedding_optimizer / --Adam_MLP_optimizer) they keep lr and their gradients are
+                                 divided by world_size instead (scale_embeddings_gradients / scale_MLP_gradients, :720-730;
+                                 the top MLP is not divided)
+    optimizers        :468-482   FusedSGD / apex FusedAdam over both MLPs, SGD / torch.optim.SparseAdam over the joint table
     CudaGraphWrapper  :194-274   whole-step capture  (here: HIP graph through torch.cuda.CUDAGraph)
 and the hybrid-parallel exchange (dlrm/model/distributed.py:25-98): one all-to-all forward, one backward,
 plus the data-parallel all-reduce (mean) of the top-MLP gradients, both through torch.distributed
@@ -12,7 +16,11 @@ plus the data-parallel all-reduce (mean) of the top-MLP gradients, both through 
 
 One deliberate difference: on a gradient overflow the reference still applies the embedding update
 (embedding_optimizer.step() is called directly, main.py:606); here the sparse update is skipped together
-with the dense one (found_inf gates both), the scale is backed off exactly as GradScaler does.
+with the dense one (found_inf gates both), the scale is backed off exactly as GradScaler does.  With sparse Adam this means:
+on an overflow step the embedding rows, their exp_avg / exp_avg_sq and the embedding step counter all stay unchanged, where
+the reference would write inf / nan into the moments of the touched rows for good.  Optimizer state lives in the trainer (the
+MLPs' moments) and the JointEmbedding (the tables' moments); checkpoints do not hold it, as in the reference, so a resumed run
+starts Adam from zero moments at step 1.
 """
 from typing import Optional, Sequence
 
@@ -27,6 +35,16 @@ from ..utils import comm
 from ..utils.comm import allreduce_mean_
 from .model import DistributedDlrm
 from .placement import ExchangePlan
+
+
+def optimizer_plan(lr, world, adam_embeddings=False, adam_mlps=False):
+    """The reference's learning-rate compensation (main.py:444-452) and Adam gradient scaling (scale_embeddings_gradients /
+    scale_MLP_gradients, main.py:720-730): part -> (learning rate, divisor of its gradient).  SGD: the model-parallel parts
+    (embeddings, bottom MLP) step with lr / world; Adam: they keep lr and their gradients are divided by world; the
+    data-parallel top MLP always steps with lr on the (all-reduce mean) gradient."""
+    return {"embeddings": (lr, world) if adam_embeddings else (lr / world, 1),
+            "bottom_mlp": (lr, world) if adam_mlps else (lr / world, 1),
+            "top_mlp": (lr, 1)}
 
 
 class GradScalerState:
@@ -72,12 +90,16 @@ class DlrmTrainer:
     def __init__(self, model: DistributedDlrm, lr: float, batch_sizes_per_gpu: Sequence[int],
                  vectors_per_gpu: Optional[Sequence[int]] = None, rank: int = 0, world_size: int = 1,
                  amp: bool = True, init_scale: float = 65536.0, freeze_mlps=False, freeze_embeddings=False,
-                 process_group=None):
+                 process_group=None, adam_embeddings=False, adam_mlps=False, adam_betas=(0.9, 0.999), adam_eps=1e-8):
+        """adam_embeddings: torch.optim.SparseAdam on the joint table in place of SGD; adam_mlps: apex FusedAdam on both MLPs in
+        place of FusedSGD (betas / eps: both optimizers' defaults)."""
         self.model = model
         self.rank, self.world = rank, world_size
         self.device = model.top_model.out.weight.device
         self.pg = process_group
         self.freeze_mlps, self.freeze_embeddings = freeze_mlps, freeze_embeddings
+        self.adam_embeddings, self.adam_mlps = bool(adam_embeddings), bool(adam_mlps)
+        self.adam_betas, self.adam_eps = tuple(adam_betas), float(adam_eps)
         d = model._embedding_dim
         if vectors_per_gpu is None:
             vectors_per_gpu = [model.bottom_model.num_feature_vectors]
@@ -89,6 +111,9 @@ class DlrmTrainer:
         # device-resident learning rates (no host sync / graph friendly)
         self.lr_dp = torch.full((1,), lr, dtype=torch.float32, device=self.device)               # top model
         self.lr_mp = torch.full((1,), lr / world_size, dtype=torch.float32, device=self.device)  # bottom parts
+        # per part (embeddings, bottom MLP, top MLP): the learning rate and the gradient divisor of the reference's rules
+        self.opt_plan = optimizer_plan(lr, world_size, self.adam_embeddings, self.adam_mlps)
+        self.lr_emb = self._lr_tensor(self.opt_plan["embeddings"][0])
         top = model.top_model
         self.top_linears = top.mlp.linears + [top.out]
         bm = model.bottom_model.mlp
@@ -108,6 +133,8 @@ class DlrmTrainer:
         model.refresh_working_copies()
         self._tables = {}
         self._build_tables()
+        if self.adam_embeddings or self.adam_mlps:
+            self._build_adam()
         self.noop = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.comm_stream = torch.cuda.Stream(device=self.device) if world_size > 1 else None
         self.moving_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -152,6 +179,90 @@ class DlrmTrainer:
                     pp += [l.weight.data, l.bias.data]
                     c += [copies[i] if copies[i].shape == l.weight.shape else None, None]
             self.t_dense = mt.TensorTable([g, pp, c], mt.streaming_chunk([g]))
+
+    def _lr_tensor(self, rate):
+        """The device tensor that carries `rate` (one of optimizer_plan's rates: lr or lr / world) through set_lr_factor."""
+        if rate == self.base_lr:
+            return self.lr_dp
+        if rate == self.base_lr / self.world:
+            return self.lr_mp
+        raise ValueError("no device learning rate for %r (lr %r, world %d)" % (rate, self.base_lr, self.world))
+
+    def _build_adam(self):
+        """Device-resident Adam state: one int32 step counter per optimizer (advanced on the device only when its step is taken),
+        the embedding gradient multiplier, the MLPs' fp32 moments and ONE FusedAdam table over both MLPs (one learning rate under
+        Adam; the bottom MLP's 1 / world rides on a per-tensor gradient multiplier).  State is allocated only for the parts that
+        step (not under freeze_embeddings / freeze_mlps); the sparse update's scratch is sized here for the batch the bottom model
+        sees, so the step itself allocates nothing."""
+        dev = self.device
+        plan = self.opt_plan
+        self.emb_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.mlp_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        emb = self.model.bottom_model.embeddings
+        if self.adam_embeddings and not self.freeze_embeddings and emb is not None:
+            emb.adam_state()
+            ws = emb.workspace()
+            ws.adam_scratch_for(self.plan.global_batch, dev)
+            ws.next_for(self.plan.global_batch * emb.num_tables, dev)
+            # g = sum * inv_scale / world (scale_embeddings_gradients, then GradScaler.unscale_)
+            self.emb_div = plan["embeddings"][1]
+            self.emb_gmul = torch.full((1,), 1.0 / self.emb_div, dtype=torch.float32, device=dev)
+        if self.adam_mlps and not self.freeze_mlps:
+            # one launch over both MLPs: Adam steps them with one rate (the top MLP's); the bottom's divisor is per tensor
+            assert plan["bottom_mlp"][0] == plan["top_mlp"][0]
+            self.lr_mlp = self._lr_tensor(plan["top_mlp"][0])
+            top = self.model.top_model
+            w16 = top.mlp.working_copies() + [top.out_working_copy()]
+            parts = [(self.top_linears, self.top_grads, w16, 1.0 / plan["top_mlp"][1])]
+            if self.bot_grads is not None:
+                parts.append((self.bot_linears, self.bot_grads, self.model.bottom_model.mlp.working_copies(),
+                              1.0 / plan["bottom_mlp"][1]))
+            g, pp, mm, vv, c, mul = [], [], [], [], [], []
+            for lins, grads, copies, f in parts:
+                for i, l in enumerate(lins):
+                    for gt, pt, cp in ((grads.views[i][0], l.weight.data, copies[i] if copies[i].shape == l.weight.shape else None),
+                                       (grads.views[i][1], l.bias.data, None)):
+                        g.append(gt); pp.append(pt); c.append(cp); mul.append(f)
+                        mm.append(torch.zeros_like(pt)); vv.append(torch.zeros_like(pt))
+            self.mlp_adam_state = (mm, vv)
+            self.mlp_gmul = torch.tensor(mul, dtype=torch.float32, device=dev)
+            self.t_adam = mt.TensorTable([g, pp, mm, vv, c], mt.streaming_chunk([g]))
+
+    def _advance(self, counter):
+        """counter += 1 unless the GradScaler found an inf / nan (the step is skipped then), on the device."""
+        sc = self.scaler
+        if sc.enabled:
+            counter.add_((sc.found_inf == 0).to(torch.int32))
+        else:
+            counter.add_(1)
+
+    def _emb_adam_args(self):
+        """The sparse Adam arguments of this step (advances the embedding step counter on the current stream)."""
+        sc = self.scaler
+        self._advance(self.emb_step)
+        if sc.enabled:
+            gmul = self.emb_gmul if self.emb_div != 1 else sc.inv_scale
+            if self.emb_div != 1:
+                torch.mul(sc.inv_scale, 1.0 / self.emb_div, out=self.emb_gmul)
+        else:
+            gmul = self.emb_gmul
+        return dict(step=self.emb_step, grad_mul=gmul, betas=self.adam_betas, eps=self.adam_eps)
+
+    def _dense_adam_step(self):
+        sc = self.scaler
+        self._advance(self.mlp_step)
+        mt.adam_copy(self.t_adam, self.lr_mlp, self.mlp_step, beta1=self.adam_betas[0], beta2=self.adam_betas[1], eps=self.adam_eps,
+                     skip_flag=sc.found_inf if sc.enabled else None, inv_scale=sc.inv_scale if sc.enabled else None,
+                     tensor_mul=self.mlp_gmul)
+        top = self.model.top_model
+        copies = top.mlp.working_copies() + [top.out_working_copy()]
+        for i in self.top_padded:
+            F.cast_rows(self.top_linears[i].weight.data, copies[i].dtype, cols_out=copies[i].shape[1], out=copies[i])
+        if self.bot_grads is not None:
+            bm = self.model.bottom_model.mlp
+            for i in self.bot_padded:
+                cp = bm.working_copies()[i]
+                F.cast_rows(self.bot_linears[i].weight.data, cp.dtype, cols_out=cp.shape[1], out=cp)
 
     def set_lr_factor(self, factor: float):
         """LearningRateScheduler.step() (dlrm/scripts/utils.py:278-286): lr = base * factor per group."""
@@ -336,10 +447,13 @@ class DlrmTrainer:
                 # grad_bottom is this rank's slice of a model-parallel gradient: ranks must agree on skipping the step
                 # (torch's GradScaler all-reduces found_inf across the process group in the same way)
                 comm.allreduce_max_(sc.found_inf, self.pg)
-        m.bottom_model.backward(grad_bottom, self.lr_mp, inv_scale=sc.inv_scale if sc.enabled else None,
+        emb_adam = None
+        if self.adam_embeddings and not self.freeze_embeddings and m.bottom_model.embeddings is not None:
+            emb_adam = self._emb_adam_args()
+        m.bottom_model.backward(grad_bottom, self.lr_emb, inv_scale=sc.inv_scale if sc.enabled else None,
                                 skip_flag=sc.found_inf if sc.enabled else None,
                                 mlp_grads=self.bot_grads.views if self.bot_grads is not None else None,
-                                freeze_embeddings=self.freeze_embeddings)
+                                freeze_embeddings=self.freeze_embeddings, emb_adam=emb_adam)
         if self.world > 1:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
         elif self._wgrad_stream() is not None:
@@ -349,6 +463,9 @@ class DlrmTrainer:
             if self.world > 1:
                 comm.allreduce_max_(sc.found_inf, self.pg)
         if not self.freeze_mlps:
-            self._dense_step()
+            if self.adam_mlps:
+                self._dense_adam_step()
+            else:
+                self._dense_step()
         sc.update()
         return loss

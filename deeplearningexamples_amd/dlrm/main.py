@@ -113,8 +113,9 @@ def parse_flags(argv=None):
     f = build_parser().parse_args(argv)
     if f.mode == "inference_benchmark":
         raise SystemExit("--mode inference_benchmark: inference is outside this path (the train step and its validation pass)")
-    if f.Adam_embedding_optimizer or f.Adam_MLP_optimizer:
-        raise SystemExit("--Adam_*_optimizer: the path implements the reference's default SGD recipe")
+    if (f.Adam_embedding_optimizer or f.Adam_MLP_optimizer) and f.embedding_sharding == "row":
+        raise SystemExit("--Adam_embedding_optimizer / --Adam_MLP_optimizer: Adam runs on the table-wise placement only "
+                         "(--embedding_sharding table); the row-sharded trainer implements SGD")
     if f.interaction_op == "cat":
         raise SystemExit("--interaction_op cat: the path implements the dot interaction (cuda_dot / dot), the reference's default")
     if (f.dataset_type == "parametric" or f.synthetic_dataset_use_feature_spec) and f.dataset is None:
@@ -162,7 +163,8 @@ def main(argv=None):
         world_size=world, bottom_features_ordered=flags.bottom_features_ordered)
     trainer = DlrmTrainer(model, lr=flags.lr, batch_sizes_per_gpu=batch_sizes, vectors_per_gpu=mapping["vectors_per_gpu"],
                           rank=rank, world_size=world, amp=flags.amp, freeze_mlps=flags.freeze_mlps,
-                          freeze_embeddings=flags.freeze_embeddings)
+                          freeze_embeddings=flags.freeze_embeddings, adam_embeddings=flags.Adam_embedding_optimizer,
+                          adam_mlps=flags.Adam_MLP_optimizer)
     sched = LearningRateScheduler(flags.warmup_steps, flags.warmup_factor, flags.decay_steps, flags.decay_start_step,
                                   flags.decay_power, flags.decay_end_lr / flags.lr)
     writer = ckpt.make_distributed_checkpoint_writer(mapping, rank, is_main_process(), dict(vars(flags)))

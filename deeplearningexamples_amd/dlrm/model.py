@@ -250,6 +250,22 @@ class JointEmbedding(nn.Module):
         F.emb_sgd_dedup_(self.weight.data, self._rows, grad, self.workspace(), lr, scale=inv_scale,
                          skip_flag=skip_flag, grad_batch_stride=grad_batch_stride)
 
+    def adam_state(self):
+        """(exp_avg, exp_avg_sq): fp32 tables of the weight's shape, zero until the first sparse Adam step, allocated on first use
+        (nothing on the SGD path).  Not part of the state_dict: the reference's checkpoints hold no optimizer state either."""
+        if getattr(self, "_adam_m", None) is None:
+            self._adam_m = torch.zeros_like(self.weight.data)
+            self._adam_v = torch.zeros_like(self.weight.data)
+        return self._adam_m, self._adam_v
+
+    def apply_sparse_adam(self, grad, lr, step, grad_mul=None, skip_flag=None, grad_batch_stride=0, betas=(0.9, 0.999),
+                          eps=1e-8):
+        """torch.optim.SparseAdam (defaults betas (0.9, 0.999), eps 1e-8) on the rows the last forward looked up, from the 16-bit
+        upstream gradient: g = (sum of a row's gradients) * grad_mul; `step` int32 device [1] = t of this update."""
+        m, v = self.adam_state()
+        F.emb_adam_dedup_(self.weight.data, m, v, self._rows, grad, self.workspace(), lr, step, grad_mul=grad_mul,
+                          skip_flag=skip_flag, betas=betas, eps=eps, grad_batch_stride=grad_batch_stride)
+
 
 class DotInteraction(nn.Module):
     """[x0 | strict lower triangle of X X^T | zero pad to a multiple of 8]  (interactions.py:40-101)."""
@@ -337,9 +353,10 @@ class DlrmBottom(nn.Module):
             self._side = torch.cuda.Stream(device=dev)
         return self._side
 
-    def backward(self, grad_out, emb_lr, inv_scale=None, skip_flag=None, mlp_grads=None, freeze_embeddings=False):
-        """grad_out [B, n_local, D] 16-bit.  Embedding rows are updated in place (fused sparse SGD);
-        bottom-MLP gradients are produced for the dense optimizer."""
+    def backward(self, grad_out, emb_lr, inv_scale=None, skip_flag=None, mlp_grads=None, freeze_embeddings=False, emb_adam=None):
+        """grad_out [B, n_local, D] 16-bit.  Embedding rows are updated in place (fused sparse SGD, or sparse Adam when
+        emb_adam = dict(step=, grad_mul=[, betas=, eps=]) is given: learning rate emb_lr, gradient multiplier grad_mul in place of
+        inv_scale); bottom-MLP gradients are produced for the dense optimizer."""
         n_vec, d = self.num_feature_vectors, self._embedding_dim
         slot = 1 if self.mlp is not None else 0
         both = self.embeddings is not None and not freeze_embeddings and self.mlp is not None
@@ -348,8 +365,12 @@ class DlrmBottom(nn.Module):
             side.wait_stream(torch.cuda.current_stream())
         if self.embeddings is not None and not freeze_embeddings:
             with (torch.cuda.stream(side) if side is not None else _nullcontext()):
-                self.embeddings.apply_sparse_sgd(grad_out[:, slot:, :], emb_lr, inv_scale, skip_flag,
-                                                 grad_batch_stride=n_vec * d)
+                if emb_adam is not None:
+                    self.embeddings.apply_sparse_adam(grad_out[:, slot:, :], emb_lr, skip_flag=skip_flag,
+                                                      grad_batch_stride=n_vec * d, **emb_adam)
+                else:
+                    self.embeddings.apply_sparse_sgd(grad_out[:, slot:, :], emb_lr, inv_scale, skip_flag,
+                                                     grad_batch_stride=n_vec * d)
         if self.mlp is not None:
             self.mlp.backward(grad_out[:, 0, :], grads=mlp_grads)
         if side is not None:                       # joined here: the caller may now raise found_inf for the dense gradients

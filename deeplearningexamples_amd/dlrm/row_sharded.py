@@ -100,6 +100,8 @@ def grad_exchange(g_send, c_send, c_recv, world, group):
 class RowShardedDlrmTrainer(DlrmTrainer):
     def __init__(self, model: DistributedDlrm, plan: RowShardPlan, lr: float, batch_sizes_per_gpu: Sequence[int], rank=0,
                  world_size=1, **kw):
+        if kw.get("adam_embeddings") or kw.get("adam_mlps"):
+            raise ValueError("row-sharded placement: SGD only (Adam runs on the table-wise placement)")
         t = len(plan.sizes)
         super().__init__(model, lr, batch_sizes_per_gpu, vectors_per_gpu=[t + 1] * world_size, rank=rank, world_size=world_size, **kw)
         if model._hash_indices:

@@ -157,6 +157,15 @@ class EmbUpdateWorkspace:
             self.next = torch.empty(n, dtype=torch.int32, device=device)
         return self.next
 
+    def adam_scratch_for(self, batch, device):
+        """Scratch of the sparse Adam update (dle_emb_adam_workspace_bytes), kept apart from the SGD's and grown on demand."""
+        import ctypes
+        need = int(C.lib().dle_emb_adam_workspace_bytes(self.offsets_host.ctypes.data_as(ctypes.c_void_p), self.tables, self.dim,
+                                                        batch))
+        if getattr(self, "adam_scratch", None) is None or self.adam_scratch.numel() * 4 < max(need, 4):
+            self.adam_scratch = torch.empty(max((need + 3) // 4, 1), dtype=torch.float32, device=device)
+        return self.adam_scratch
+
 
 def emb_sgd_dedup_(weight, rows, grad, ws, lr, scale=None, skip_flag=None, grad_batch_stride=0):
     """In place W[rows[b,t]] -= lr*scale*grad[b,t] with duplicate rows summed first (no float atomics).
@@ -179,6 +188,44 @@ def emb_sgd_dedup_(weight, rows, grad, ws, lr, scale=None, skip_flag=None, grad_
            C.ptr(ws.is_small), ws.offsets_host.ctypes.data_as(ctypes.c_void_p), C.ptr(lr_dev), lr_host,
            C.ptr(scale), C.ptr(skip_flag), b, t, ws.dim, grad_batch_stride, C.dt(grad), C.ptr(oh),
            oh.numel() * 4 if oh is not None else 0, C.stream())
+    return weight
+
+
+def emb_adam_dedup_(weight, exp_avg, exp_avg_sq, rows, grad, ws, lr, step, grad_mul=None, skip_flag=None, betas=(0.9, 0.999),
+                    eps=1e-8, grad_batch_stride=0, touched_rows=None):
+    """torch.optim.SparseAdam on the rows `rows` looks up, in place: duplicates of a row are summed (fp32) first, then every
+    looked-up row -- one whose sum is 0 included -- takes one step with g = sum * grad_mul; other rows keep w / m / v bit for bit.
+    weight / exp_avg / exp_avg_sq: contiguous fp32 [rows, dim]; rows int64 [B,T]; grad as for emb_sgd_dedup_; step: int32 device
+    tensor [1] holding t of THIS update; lr: float or fp32 device tensor [1]; grad_mul / skip_flag: fp32 device tensors [1] or None.
+    touched_rows (optional, host int): distinct rows of the batch, for the algorithmic byte count of a kernel timer (without it
+    the count covers the gradient reads and row ids only)."""
+    import ctypes
+    C.require_cuda(weight, exp_avg, exp_avg_sq, rows, grad, step, grad_mul, skip_flag)
+    for name, x in (("embedding table", weight), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("%s must be contiguous fp32" % name)
+    if exp_avg.shape != weight.shape or exp_avg_sq.shape != weight.shape:
+        raise ValueError("exp_avg / exp_avg_sq must have the table's shape %s" % (tuple(weight.shape),))
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise ValueError("step must be an int32 device tensor of one element")
+    if grad.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError("gradient dtype %s: fp32, fp16 or bf16" % grad.dtype)
+    rows = _i64(rows, "rows")
+    b, t = rows.shape
+    if t != ws.tables or weight.shape[1] != ws.dim:
+        raise ValueError("workspace was built for %d tables x dim %d" % (ws.tables, ws.dim))
+    lr_dev = lr if isinstance(lr, torch.Tensor) else None
+    lr_host = 0.0 if lr_dev is not None else float(lr)
+    nxt = ws.next_for(b * t, weight.device)
+    scratch = ws.adam_scratch_for(b, weight.device)
+    # algorithmic: gradient row + row id per lookup, plus w, m, v read + written per touched row when that count is given (without
+    # it the count would need a host read-back: the annotation is then the lower, gradient-side bound)
+    table_side = 0.0 if touched_rows is None else float(touched_rows) * 6 * ws.dim * 4
+    C.annotate(bytes=table_side + float(b) * t * (ws.dim * grad.element_size() + 8))
+    C.call("dle_emb_adam_dedup_ws", C.ptr(weight), C.ptr(exp_avg), C.ptr(exp_avg_sq), C.ptr(rows), C.ptr(grad), C.ptr(ws.head),
+           C.ptr(nxt), ws.offsets_host.ctypes.data_as(ctypes.c_void_p), C.ptr(lr_dev), lr_host, C.ptr(grad_mul), C.ptr(skip_flag),
+           C.ptr(step), 1.0 - float(betas[0]), 1.0 - float(betas[1]), float(eps), b, t, ws.dim, grad_batch_stride, C.dt(grad), C.ptr(scratch),
+           scratch.numel() * 4, C.stream())
     return weight
 
 

@@ -158,3 +158,22 @@ def adam(table, lr, beta1, beta2, eps, weight_decay, step, skip_flag=None, inv_s
     C.call("dle_mt_adam", C.ptr(table.table), table.n, table.total_chunks, table.chunk, C.ptr(skip_flag), C.ptr(lr_dev),
            0.0 if lr_dev is not None else float(lr), beta1, beta2, eps, weight_decay, C.ptr(step), C.ptr(inv_scale),
            C.ptr(grad_norm), float(max_grad_norm if grad_norm is not None else 0.0), C.stream())
+
+
+def adam_copy(table, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, skip_flag=None, inv_scale=None, tensor_mul=None,
+              model_copy=True):
+    """apex FusedAdam (bias_correction, weight_decay 0) behind GradScaler.step, with the 16-bit working copies refreshed in the
+    same pass.  lists: g, p, exp_avg, exp_avg_sq (fp32) [, 16-bit copy of p (model_copy=True; None entries: tensors without one)].
+    grad = g * inv_scale * tensor_mul[i]: tensor_mul is an fp32 device tensor [n] (the 1 / world of the bottom MLP) or None;
+    `step` = int32 device word holding THIS update's step number."""
+    want = 5 if model_copy else 4
+    if table.n_lists != want or any(d != torch.float32 for d in table.dtypes[:4]):
+        raise ValueError("adam_copy expects four fp32 lists g, p, exp_avg, exp_avg_sq%s" % (" and the copies" if model_copy else ""))
+    if tensor_mul is not None and (tensor_mul.dtype != torch.float32 or tensor_mul.numel() != table.n):
+        raise ValueError("tensor_mul: fp32 [%d]" % table.n)
+    lr_dev = lr if isinstance(lr, torch.Tensor) else None
+    copy_dt = C.dt(table.dtypes[-1]) if model_copy else -1
+    _note(table, 7 * 4 + (2 if model_copy else 0))
+    C.call("dle_mt_adam_copy", C.ptr(table.table), table.n, table.total_chunks, table.chunk, copy_dt, C.ptr(skip_flag), C.ptr(lr_dev),
+           0.0 if lr_dev is not None else float(lr), beta1, beta2, eps, C.ptr(step), C.ptr(inv_scale), C.ptr(tensor_mul),
+           C.stream())

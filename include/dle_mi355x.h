@@ -112,6 +112,30 @@ int dle_emb_onehot_try(float* weight, const int64_t* rows, const void* grad, con
                        const int* tab_rows, int n_tab, int64_t batch, int tables, int dim, int64_t grad_batch_stride,
                        int grad_dtype, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* The one-hot segment sums alone (no update): fp32 partial blocks ws[k][slice][r][128] for r < tab_rows[k], *slices_out = the
+ * slice count; the sparse Adam update folds them itself.  1: launched, 0: outside the kernel's envelope, > 1: error. */
+int dle_emb_onehot_partials(const int64_t* rows, const void* grad, const float* skip_flag_dev, const int* tab_t,
+                            const int64_t* tab_base, const int* tab_rows, int n_tab, int64_t batch, int tables, int dim,
+                            int64_t grad_batch_stride, int grad_dtype, void* ws, int64_t ws_bytes, int* slices_out,
+                            hipStream_t stream);
+
+/* ---- duplicate-free sparse Adam on the joint table (csrc/emb_adam.hip): torch.optim.SparseAdam over the joint embedding
+ * (DLRM/dlrm/scripts/main.py:479-482, torch.optim._functional.sparse_adam) behind --Adam_embedding_optimizer.  Duplicate
+ * lookups are summed in fp32 first; every looked-up row -- a row whose sum is exactly 0 included -- takes ONE step
+ *   m += (1-b1)(g-m);  v += (1-b2)(g^2-v);  w -= lr sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps),   g = sum * (*grad_mul_dev)
+ * and every other row keeps w, exp_avg (m) and exp_avg_sq (v) bit for bit.  No float atomics in global memory, no host
+ * synchronisation or allocation (graph capturable).  w, m, v: fp32 [total rows, dim]; rows int64 [batch, tables] joint ids; grad
+ * fp32 / fp16 / bf16, row (b,t) at grad + b*grad_batch_stride + t*dim (stride 0 = tables*dim); head / next as for
+ * dle_emb_sgd_dedup_ws (head all -1 on entry and on exit); step_dev: int32 device word = t of THIS update (the caller advances
+ * it); skip_flag_dev != 0: nothing is written.  The betas are passed as 1 - beta (1 - 0.999f would be 1.3e-5 off
+ * the 1e-3 the reference multiplies v by).  ws: dle_emb_adam_workspace_bytes() bytes, 256-byte aligned.  tables <= 128. */
+int64_t dle_emb_adam_workspace_bytes(const int64_t* table_offsets_host, int tables, int dim, int64_t batch);
+int dle_emb_adam_dedup_ws(float* weight, float* exp_avg, float* exp_avg_sq, const int64_t* rows, const void* grad, int32_t* head,
+                          int32_t* next, const int64_t* table_offsets_host, const float* lr_dev, float lr_host,
+                          const float* grad_mul_dev, const float* skip_flag_dev, const int32_t* step_dev, float one_minus_beta1,
+                          float one_minus_beta2, float eps, int64_t batch, int tables, int dim, int64_t grad_batch_stride, int grad_dtype, void* ws,
+                          int64_t ws_bytes, hipStream_t stream);
+
 /* ---- dense contraction with fused epilogue ---------------------------------------------------
  * replaces cuBLAS GEMM + NVFuser/apex epilogues: apex.mlp (Recommendation/DLRM/dlrm/nn/mlps.py:18-43),
  * F.linear + bias + gelu (LanguageModeling/BERT/modeling.py:130-165), RN50 fc.
@@ -551,6 +575,15 @@ int dle_mt_adam(const int64_t* table_dev, int n_tensors, int64_t total_chunks, i
                 const float* lr_dev, float lr_host, float beta1, float beta2, float eps, float weight_decay,
                 const int* step_dev, const float* inv_scale_dev, const float* grad_norm_dev, float max_grad_norm,
                 hipStream_t stream);
+
+/* ---- apex FusedAdam (bias_correction, weight_decay 0) with the 16-bit working-copy refresh (csrc/multi_tensor.hip): DLRM's
+ * --Adam_MLP_optimizer (Recommendation/DLRM/dlrm/scripts/main.py:468-471).  lists: g, p, exp_avg, exp_avg_sq (fp32) and a 16-bit
+ * copy of p (copy_dtype; pointer 0 where a tensor has none, copy_dtype -1: no copy list).  grad = g * inv_scale *
+ * tensor_mul_dev[tensor] (fp32 [n_tensors] or NULL); step_dev: int32 device word = t of THIS update; skip_flag_dev != 0: the
+ * step is skipped. */
+int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, int copy_dtype,
+                     const float* skip_flag_dev, const float* lr_dev, float lr_host, float beta1, float beta2, float eps,
+                     const int* step_dev, const float* inv_scale_dev, const float* tensor_mul_dev, hipStream_t stream);
 
 /* ---- WaveGlow training step (csrc/waveglow.hip): SpeechSynthesis/Tacotron2/waveglow/model.py + loss_function.py -------
  * Channels-last: a series [B, C, T] of the reference is the matrix [B*T, C]; Conv1d = dle_gemm over rows.  The flow state
