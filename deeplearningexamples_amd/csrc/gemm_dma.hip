@@ -1097,6 +1097,7 @@ extern "C" int dle_gemm_colsum_bits(const void* A, const void* B, void* C, const
 // (Classification/ConvNets/image_classification/models/common.py:31-60, resnet.py:126-175).
 extern "C" int dle_conv3x3_try(const void* x, const void* w, void* y, float* stats, long long stats_bytes, int N, int H,
                                int W, int C, int Ko, int dgrad, int dtype, hipStream_t stream);   // conv3x3.hip
+extern "C" int dle_conv3x3_tiles(int N, int H, int W);                                          // conv3x3.hip
 
 static int conv_launch(Gemm2Args& p, int in_dtype, int amode, int bmode, hipStream_t stream) {
   return launch_gemm(p, in_dtype, amode, bmode, 0, stream);
@@ -1156,7 +1157,9 @@ extern "C" int dle_conv2d_fwd_colstats(const void* x, const void* w, void* y, in
   const int g = (int)((M + BM - 1) / BM);
   DLE_CHECK_ARG(col_partial_bytes >= (long long)g * 2 * Ko * 4, "conv2d_fwd_colstats: partial buffer too small (%lld tile rows)", (long long)g);
   *groups = g;
-  if (R == 3 && S == 3 && stride == 1 && pad == 1) {
+  // the halo kernel writes one row per 256 PADDED slots, ceil(N (H+1) (W+2) / 256): more than the ceil(M / 128) rows the caller
+  // had to provide when H is small (H = 1: 2 (W+2) slots per 128-row tile of W pixels); it only runs when the buffer holds them
+  if (R == 3 && S == 3 && stride == 1 && pad == 1 && col_partial_bytes >= (long long)dle_conv3x3_tiles(N, H, W) * 2 * Ko * 4) {
     const int rc = dle_conv3x3_try(x, w, y, col_partial, col_partial_bytes, N, H, W, C, Ko, 0, dtype, stream);
     if (rc == 1) { *groups = (int)(((long long)N * (H + 1) * (W + 2) + 255) / 256); return 0; }
     if (rc > 1) return rc;

@@ -1,0 +1,530 @@
+"""The stand-alone BatchNorm kernels of csrc/convnet.hip against a float64 restatement of nn.BatchNorm2d(train), at the ResNet-50
+batch-256 sizes the step runs.  GPU only.
+
+The fused kernels (conv_bnload, conv_bnbwd, gemm_masked_add_bnred, bn_reduce2, bn_apply2, bn_relu_maxpool, pool_bn_bwd) are tested
+as bit-identical to these, so this file is what ties the whole BatchNorm chain to the operation it implements.  The reference is
+
+    y  = act((x - mean) rstd gamma + beta (+ residual)),  mean = E x,  rstd = 1 / sqrt(E x^2 - mean^2 + eps)   (biased variance)
+    running_mean = (1 - momentum) running_mean + momentum mean,  running_var likewise with the unbiased variance
+    dx = gamma rstd (g - E g - xhat E[g xhat]),  g = dy keep,  dgamma = sum g xhat,  dbeta = sum g
+
+computed by torch in float64 on the GPU (torch's own kernels, not this library's).  The (M, C) cases are the batch-256 families
+(802816, 64), (802816, 256), (200704, 128), (200704, 512), (50176, 256), (50176, 1024), (12544, 2048) and ragged ones: M a prime
+one to eight rows past a row-group boundary, C = 24, 72 (C / 8 does not divide the apply grid: the non-prefetched apply kernels),
+520 (65 column lanes over three 32-lane column blocks, the last one holding a single lane).  They reach 197 ... 1024 row groups
+of the reduction with its 8-row batches and remainder loop, the lanes-per-row cap (C = 1024, 2048), and 1 ... 25 grid-stride
+trips of the apply kernels with the peeled first and partial last trip.
+
+Exactly summable inputs.  Activations and gradients are drawn from k / 4, |k| <= 4 (exact in fp16 and bf16).  Every term of every
+column sum (x, x^2, g, g xhat with mean 0 and rstd 1 or 2) is then a multiple of 1/16, and while the sum of the magnitudes stays
+below 2^20 (checked from the data by _check_exact) every partial sum in any order has at most 24 significant bits: the fp32 sums are
+EXACT, whatever the kernel's summation order.  So:
+* mean = S0 / M is one correctly rounded division in both: bit-identical.  dgamma, dbeta are exact sums: bit-identical.
+* rstd is 1 / sqrt(S1 / M - mean^2 + eps) in double then rounded to fp32; the kernel's compiler may contract mean^2 into an fma,
+  which moves the double result by ~1e-16 relative, so the fp32 rstd may sit one ulp away: bar 1 fp32 ulp.
+* running stats are one fp32 multiply-add each of (1 - momentum) r and momentum v (v = mean, or the unbiased variance rounded to
+  fp32): <= 3 roundings of u = 2^-24 relative to the magnitudes, plus u for rounding v: bar 4 u (|(1 - momentum) r| + |momentum v|).
+A single missing, repeated or misplaced row, group or channel then fails at once, at M = 802816 as at M = 12544.
+
+Realistic inputs (test_fwd_stats_gaussian): Gaussian columns, sigma in [0.5, 1.5], mean offsets up to 4 sigma, and one constant
+column (variance 0: E x^2 - mean^2 cancels completely, rstd = 1 / sqrt(eps)).  The reduction is a chain of ceil(rows per group /
+rows per step) fp32 additions per lane, then a chain of `rows per step` within the workgroup, then fp64: with n the sum of the two
+chain lengths, |dS0| <= n u sum |x| and |dS1| <= n u sum x^2 (Higham's gamma_n).  So |d mean| <= n u E|x| + u |mean|,
+|d var| <= n u (E x^2 + 2 |mean| E|x|), and with r = |d var| / (var + eps) the relative error of rstd is below (1 - r)^(-1/2) - 1
++ 2 u.  For the constant column r reaches 1e-2 (E x^2 = 0.09 against eps = 1e-5): the bar follows.
+
+Apply (bn_fwd_apply): y is rounded once to 16 bits.  Its fp32 arithmetic (sc = rstd gamma, sh = beta - mean sc, x sc + sh (+ r))
+errs by e <= 6 u (|x sc| + |mean sc| + |beta| + |r|), so y lies within 1 ulp (16-bit, at the larger of |y|, |ref|) + e + 2 u |ref|
+of the float64 value rounded to 16 bits (the last term: torch rounds fp64 -> 16 bits through fp32).  The keep bits must equal
+y > 0 exactly.  Outputs go into over-long buffers filled with a sentinel: the kernel's writes must cover [0, M C) and stop there.
+
+Backward apply (bn_bwd dx): the bar of test_gpu_conv_bnbwd, 1.5 x the 16-bit step (2^-10 fp16, 2^-7 bf16) x max |ref|: one
+rounding of the output and of the fp32 chain g - dbeta / M - xhat dgamma / M (1 / M rounded to fp32).  g_out = dy keep is exact.
+
+Convolution producers (conv2d_fwd_bnstats, stem_conv_fwd_bnstats) run with one-hot weights, a different (tap, channel) per output
+channel, so y is an exact shifted copy of x, zero where the tap reads padding: y must equal that copy bit for bit and the
+statistics of the stored y are exact as above (the halo kernel's computed-and-dropped padding slots must not enter them).  Which
+kernel took the launch is asserted from the partial-row count dle_conv2d_fwd_colstats reports and gemm8's launch counter.
+
+DLE_BN_PF and DLE_BN_FINISH_WIDE are read once per process; this file covers the default dispatch.
+"""
+import ctypes
+
+import pytest
+import torch
+
+from deeplearningexamples_amd import _cabi as C
+from deeplearningexamples_amd import functional as F
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+EPS = 1e-5
+EPS64 = float(torch.tensor(EPS, dtype=torch.float32))      # the fp32 argument as the kernels widen it
+MOM = 0.1
+MOM32 = torch.tensor(MOM, dtype=torch.float32)
+ONE_MINUS_MOM = float(torch.tensor(1.0, dtype=torch.float32) - MOM32)   # (1.f - momentum), in fp32
+MANT = {torch.float16: 10, torch.bfloat16: 7}
+EMIN = {torch.float16: -14, torch.bfloat16: -126}
+STEP = {torch.float16: 2.0 ** -10, torch.bfloat16: 2.0 ** -7}
+BF, HF = torch.bfloat16, torch.float16
+
+# batch-256 ResNet-50 (M = N H W, C) families, then ragged: primes 1..8 rows past a row-group boundary of the reduction
+RN50 = [(802816, 64), (802816, 256), (200704, 128), (200704, 512), (50176, 256), (50176, 1024), (12544, 2048)]
+RAGGED = [(100357, 24), (150089, 72), (60521, 520), (401017, 64)]
+SHAPES = RN50 + RAGGED
+FP16_SHAPES = [(802816, 64), (50176, 1024), (12544, 2048), (150089, 72), (60521, 520)]
+CASES = [(BF, m, c) for m, c in SHAPES] + [(HF, m, c) for m, c in FP16_SHAPES]
+CASE_IDS = ["%s-%dx%d" % ("bf16" if d == BF else "fp16", m, c) for d, m, c in CASES]
+GROUPS = [1, 31, 32, 33, 1100, 1101, 3306, 25088]
+
+
+def _gen(dev, seed):
+    return torch.Generator(device=dev).manual_seed(seed)
+
+
+def _grid(shape, seed, dtype, dev, kmax=4):
+    """k / 4 with |k| <= kmax: exact in fp16 and bf16, squares and products of two multiples of 1/16."""
+    k = torch.randint(-kmax, kmax + 1, shape, generator=_gen(dev, seed), device=dev)
+    return (k.float() * 0.25).to(dtype)
+
+
+def _check_exact(*terms):
+    """Precondition of the bit-exact bars: every term [M, C] (float64) is a multiple of 1/16 and each column's sum of magnitudes is
+    below 2^20, so every partial sum, in any order, is a multiple of 1/16 below 2^20: at most 24 significant bits, exact in fp32."""
+    for t in terms:
+        assert torch.equal(t * 16, torch.round(t * 16)), "term off the 1/16 grid"
+        worst = float(t.abs().sum(0).max())
+        assert worst < 2.0 ** 20, "column magnitude sum %g: fp32 sums would not be exact" % worst
+
+
+def _ulp32(v):
+    """fp32 spacing at |v| (v float64, normal range)."""
+    _, e = torch.frexp(v.abs())
+    return torch.pow(2.0, (e - 24).double())
+
+
+def _ulp16(v, dtype):
+    """Spacing of `dtype` at |v| (float64), the subnormal spacing at and near 0."""
+    _, e = torch.frexp(v.abs())
+    e = torch.where(v == 0, torch.full_like(e, EMIN[dtype] + 1), e)
+    return torch.pow(2.0, (e - 1).clamp_min(EMIN[dtype]).double() - MANT[dtype])
+
+
+def _unpack_bits(mask, n):
+    return ((mask[:n // 8].to(torch.int32).unsqueeze(1) >> torch.arange(8, device=mask.device, dtype=torch.int32)) & 1).reshape(-1).bool()
+
+
+def _pack_bits(keep):
+    b = keep.reshape(-1, 8).to(torch.int32) << torch.arange(8, dtype=torch.int32, device=keep.device)
+    return b.sum(1).to(torch.uint8)
+
+
+def _geometry(m, c):
+    """bn_reduce_geometry (csrc/convnet.hip) at its defaults: lanes per row, rows per step, rows per group, groups."""
+    lpr = 1
+    while lpr < c // 8 and lpr < 32:
+        lpr <<= 1
+    gx = (c // 8 + lpr - 1) // lpr
+    want = max(1, 1024 // gx)
+    rpb = max((m + want - 1) // want, 8 * (256 // lpr))
+    return lpr, 256 // lpr, rpb, (m + rpb - 1) // rpb
+
+
+def _running_init(c, dev, seed):
+    g = _gen(dev, seed)
+    return torch.randn(c, generator=g, device=dev), torch.rand(c, generator=g, device=dev) + 0.5
+
+
+def _assert_stats(mean, rstd, rm, rv, rm0, rv0, s0, s1, m, what):
+    """Exact fp32 column sums s0, s1 (float64) of m rows -> the bars of the module docstring."""
+    rmean = s0 / m
+    var = (s1 / m - rmean * rmean).clamp_min(0.0)
+    rrstd = 1.0 / torch.sqrt(var + EPS64)
+    assert torch.equal(mean, rmean.float()), "%s: mean differs from S0 / M at %s" % (what, torch.nonzero(mean != rmean.float())[:4].tolist())
+    d = (rstd.double() - rrstd).abs()
+    assert bool((d <= _ulp32(rrstd)).all()), "%s: rstd off by %g ulp" % (what, float((d / _ulp32(rrstd)).max()))
+    if rm is None:
+        return
+    unb = (var * m / (m - 1)).float().double()
+    mom = float(MOM32)
+    ref_m = ONE_MINUS_MOM * rm0.double() + mom * mean.double()
+    ref_v = ONE_MINUS_MOM * rv0.double() + mom * unb
+    bar_m = 4 * U * (ONE_MINUS_MOM * rm0.double().abs() + mom * mean.double().abs())
+    bar_v = 4 * U * (ONE_MINUS_MOM * rv0.double().abs() + mom * unb.abs())
+    assert bool(((rm.double() - ref_m).abs() <= bar_m).all()), "%s: running_mean" % what
+    assert bool(((rv.double() - ref_v).abs() <= bar_v).all()), "%s: running_var" % what
+
+
+def _fwd_stats(x, rm, rv):
+    m, c = x.shape
+    nbytes = int(C.lib().dle_bn_workspace_bytes(m, c))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    mean = torch.full((c,), float("nan"), device=x.device)
+    rstd = torch.full((c,), float("nan"), device=x.device)
+    C.call("dle_bn_fwd_stats", C.ptr(x), m, c, EPS, MOM, C.ptr(mean), C.ptr(rstd), C.ptr(rm), C.ptr(rv), C.ptr(ws), nbytes, C.dt(x),
+           C.stream())
+    return mean, rstd
+
+
+def _stats_from_partials(part, groups, m, c, rm, rv):
+    mean = torch.full((c,), float("nan"), device=part.device)
+    rstd = torch.full((c,), float("nan"), device=part.device)
+    ws = torch.empty(32 * 2 * c, dtype=torch.float32, device=part.device)
+    C.call("dle_bn_stats_from_partials", C.ptr(part), groups, m, c, EPS, MOM, C.ptr(mean), C.ptr(rstd), C.ptr(rm), C.ptr(rv), C.ptr(ws),
+           ws.numel() * 4, C.stream())
+    return mean, rstd
+
+
+# ---------------------------------------------------------------- statistics
+@pytest.mark.parametrize("c", [64, 520])
+@pytest.mark.parametrize("groups", GROUPS)
+def test_stats_from_partials(cuda, groups, c):
+    """Synthetic partial rows [groups][2][C]: 1 ... 32 groups -> finish, 33 ... 1100 -> the wide finish, > 1100 -> fold + finish."""
+    g = _gen(cuda, 1000 * groups + c)
+    s0 = torch.randint(-256, 257, (groups, c), generator=g, device=cuda).double() / 16
+    s1 = torch.randint(16, 512, (groups, c), generator=g, device=cuda).double() / 16
+    _check_exact(s0, s1)
+    part = torch.stack([s0, s1], 1).float().contiguous()
+    m = 128 * groups
+    rm0, rv0 = _running_init(c, cuda, groups)
+    rm, rv = rm0.clone(), rv0.clone()
+    mean, rstd = _stats_from_partials(part, groups, m, c, rm, rv)
+    _assert_stats(mean, rstd, rm, rv, rm0, rv0, s0.sum(0), s1.sum(0), m, "groups=%d" % groups)
+    mean2, rstd2 = _stats_from_partials(part, groups, m, c, None, None)      # without running statistics
+    assert torch.equal(mean2, mean) and torch.equal(rstd2, rstd)
+
+
+@pytest.mark.parametrize("dtype, m, c", CASES, ids=CASE_IDS)
+def test_fwd_stats_exact(cuda, dtype, m, c):
+    """dle_bn_fwd_stats (bn_reduce_kernel MODE 0 + finish) on exactly summable x."""
+    x = _grid((m, c), m + c, dtype, cuda)
+    xd = x.double()
+    _check_exact(xd, xd * xd)
+    rm0, rv0 = _running_init(c, cuda, c)
+    rm, rv = rm0.clone(), rv0.clone()
+    mean, rstd = _fwd_stats(x, rm, rv)
+    _assert_stats(mean, rstd, rm, rv, rm0, rv0, xd.sum(0), (xd * xd).sum(0), m, "M=%d C=%d" % (m, c))
+
+
+@pytest.mark.parametrize("dtype, m, c", CASES, ids=CASE_IDS)
+def test_fwd_stats_gaussian(cuda, dtype, m, c):
+    """Realistic columns with offsets up to 4 sigma and one constant column: the fp32-accumulation bars of the docstring."""
+    g = _gen(cuda, 7 * m + c)
+    sigma = torch.rand(c, generator=g, device=cuda) + 0.5
+    offset = (torch.rand(c, generator=g, device=cuda) * 8 - 4) * sigma
+    x = (torch.randn((m, c), generator=g, device=cuda) * sigma + offset).to(dtype)
+    x[:, c // 3] = 0.3
+    xd = x.double()
+    rm0, rv0 = _running_init(c, cuda, c + 1)
+    rm, rv = rm0.clone(), rv0.clone()
+    mean, rstd = _fwd_stats(x, rm, rv)
+    _, rstep, rpb, _ = _geometry(m, c)
+    n = (rpb + rstep - 1) // rstep + rstep
+    a0, a1 = xd.abs().mean(0), (xd * xd).mean(0)
+    rmean = xd.mean(0)
+    var = ((xd - rmean) ** 2).mean(0)
+    rrstd = 1.0 / torch.sqrt(var + EPS64)
+    assert bool(((mean.double() - rmean).abs() <= n * U * a0 + U * rmean.abs()).all()), "mean"
+    r = n * U * (a1 + 2 * rmean.abs() * a0) / (var + EPS64)
+    assert float(r.max()) < 0.5
+    rel = (1 - r) ** -0.5 - 1 + 2 * U
+    assert bool(((rstd.double() - rrstd).abs() <= rel * rrstd).all()), "rstd: worst %g of its bar" % float(
+        ((rstd.double() - rrstd).abs() / (rel * rrstd)).max())
+    assert float(var[c // 3]) == 0.0 and float(rstd[c // 3]) == pytest.approx(EPS64 ** -0.5, rel=float(rel[c // 3]))
+    mom = float(MOM32)
+    unb = var * m / (m - 1)
+    ref_m = ONE_MINUS_MOM * rm0.double() + mom * rmean
+    ref_v = ONE_MINUS_MOM * rv0.double() + mom * unb
+    bar_m = 4 * U * (rm0.double().abs() + rmean.abs()) + mom * n * U * a0
+    bar_v = 4 * U * (rv0.double().abs() + unb.abs()) + mom * n * U * (a1 + 2 * rmean.abs() * a0) * m / (m - 1)
+    assert bool(((rm.double() - ref_m).abs() <= bar_m).all()), "running_mean"
+    assert bool(((rv.double() - ref_v).abs() <= bar_v).all()), "running_var"
+
+
+# ---------------------------------------------------------------- statistics from the convolution epilogues
+def _onehot_weight(ko, r, s, c, dtype, dev):
+    """w[ko, tap(ko), ch(ko)] = 1: y[..., ko] = x at the tap's shift, channel ch(ko)."""
+    k = torch.arange(ko)
+    tap = k % (r * s)
+    ch = (5 * k + k // (r * s)) % c
+    w = torch.zeros(ko, r * s, c)
+    w[k, tap, ch] = 1.0
+    return w.reshape(ko, r, s, c).to(dtype).to(dev), tap, ch
+
+
+def _shifted_copy(x, tap, ch, ko, r, s, stride, pad):
+    """y of the one-hot convolution, by slicing: [N, P, Q, Ko]."""
+    n, h, w, _ = x.shape
+    p, q = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    xp = torch.nn.functional.pad(x, (0, 0, pad, pad, pad, pad))
+    y = torch.empty((n, p, q, ko), dtype=x.dtype, device=x.device)
+    for t in range(r * s):
+        kos = torch.nonzero(tap == t).flatten()
+        if kos.numel() == 0:
+            continue
+        i, j = divmod(t, s)
+        win = xp[:, i:i + stride * (p - 1) + 1:stride, j:j + stride * (q - 1) + 1:stride, :]
+        y[..., kos.to(x.device)] = win.index_select(3, ch[kos].to(x.device))
+    return y
+
+
+def _colstats(x, w, stride, pad, rm, rv):
+    """conv2d_fwd_bnstats through the C ABI, with the partial buffer sized as functional.py sizes it -> (y, groups, mean, rstd)."""
+    n, h, wd, c = x.shape
+    ko, r, s, _ = w.shape
+    p, q = (h + 2 * pad - r) // stride + 1, (wd + 2 * pad - s) // stride + 1
+    m = n * p * q
+    rows = max((m + 127) // 128, min(1032, (m + 63) // 64 + 8))
+    part = torch.full((rows * 2 * ko,), float("nan"), device=x.device)
+    y = torch.empty((n, p, q, ko), dtype=x.dtype, device=x.device)
+    groups = ctypes.c_int(0)
+    C.call("dle_conv2d_fwd_colstats", C.ptr(x), C.ptr(w), C.ptr(y), n, h, wd, c, ko, r, s, stride, pad, C.dt(x), C.ptr(part),
+           part.numel() * 4, ctypes.byref(groups), C.stream())
+    mean, rstd = _stats_from_partials(part, groups.value, m, ko, rm, rv)
+    return y, groups.value, mean, rstd
+
+
+# (id, x [N, H, W, C], Ko, R = S, stride, pad, producer)
+PRODUCERS = [
+    ("halo56", (256, 56, 56, 64), 64, 3, 1, 1, "halo"),        # 3306 partial rows: fold + finish
+    ("halo28", (256, 28, 28, 128), 128, 3, 1, 1, "halo"),      # 870: wide finish
+    ("halo14", (256, 14, 14, 256), 256, 3, 1, 1, "halo"),      # 240
+    ("tile7", (256, 7, 7, 512), 512, 3, 1, 1, "tile"),         # 7 x 7: the im2col tile kernel, 98 rows
+    ("tile3s2", (256, 56, 56, 128), 128, 3, 2, 1, "tile"),     # stride 2: 1568 rows
+    ("tile1x1", (256, 56, 56, 256), 64, 1, 1, 0, "tile"),      # narrowing 1 x 1: 6272 rows, the most any producer writes
+    ("gemm8", (256, 14, 14, 256), 1024, 1, 1, 0, "gemm8"),     # deep-stage 1 x 1: gemm8 register epilogue, 392 rows
+    ("expand", (256, 56, 56, 64), 256, 1, 1, 0, "expand"),     # widening 1 x 1: streaming kernel, one row per workgroup group
+]
+
+
+PRODUCER_CASES = [p + (BF,) for p in PRODUCERS] + [p + (HF,) for p in PRODUCERS if p[0] in ("halo56", "gemm8", "expand")]
+
+
+@pytest.mark.parametrize("pid, xs, ko, rs, stride, pad, kind, dtype", PRODUCER_CASES,
+                         ids=["%s-%s" % (p[0], "bf16" if p[-1] == BF else "fp16") for p in PRODUCER_CASES])
+def test_conv_producer_stats(cuda, pid, xs, ko, rs, stride, pad, kind, dtype):
+    x = _grid(xs, sum(xs) + ko, dtype, cuda)
+    w, tap, ch = _onehot_weight(ko, rs, rs, xs[3], dtype, cuda)
+    lib = C.lib()
+    rm0, rv0 = _running_init(ko, cuda, ko)
+    rm, rv = rm0.clone(), rv0.clone()
+    n8 = lib.dle_gemm8_launch_count()
+    y, groups, mean, rstd = _colstats(x, w, stride, pad, rm, rv)
+    torch.cuda.synchronize()
+    launched8 = lib.dle_gemm8_launch_count() - n8
+    m = y.numel() // ko
+    want = {"halo": lib.dle_conv3x3_tiles(xs[0], xs[1], xs[2]), "tile": (m + 127) // 128, "gemm8": (m + 127) // 128,
+            "expand": lib.dle_gemm_expand_groups(m, ko, xs[3])}[kind]
+    assert groups == want, "%s: %d partial rows reported, %s writes %d" % (pid, groups, kind, want)
+    assert launched8 == (1 if kind == "gemm8" else 0), "%s: gemm8 launches %d" % (pid, launched8)
+    if kind == "halo":
+        assert groups != (m + 127) // 128
+    assert torch.equal(y, _shifted_copy(x, tap, ch, ko, rs, rs, stride, pad)), "%s: y is not the shifted copy" % pid
+    yd = y.reshape(m, ko).double()
+    _check_exact(yd, yd * yd)
+    _assert_stats(mean, rstd, rm, rv, rm0, rv0, yd.sum(0), (yd * yd).sum(0), m, pid)
+    y2, mean2, rstd2 = F.conv2d_fwd_bnstats(x, w, stride, pad)            # the wrapper the model calls: the same launch
+    assert torch.equal(y2, y) and torch.equal(mean2, mean) and torch.equal(rstd2, rstd)
+
+
+@pytest.mark.parametrize("dtype", [BF, HF], ids=["bf16", "fp16"])
+def test_stem_stats(cuda, dtype):
+    """stem_conv_fwd_bnstats at batch 256 (7 x 7 / 2, pad 3, 224 x 224 -> 112 x 112, M = 3211264)."""
+    n, h = 256, 224
+    x4 = _grid((n, h, h, 4), 11, dtype, cuda, kmax=2)                      # |k| <= 2 keeps sum y^2 of 3.2 M rows below 2^20
+    k = torch.arange(64)
+    tap, ch = k % 49, k % 3
+    wm = torch.zeros(64, 3, 7, 7)
+    wm[k, ch, tap // 7, tap % 7] = 1.0
+    w2 = F.stem_pack_weight(wm.to(cuda).contiguous(memory_format=torch.channels_last), dtype)
+    rm0, rv0 = _running_init(64, cuda, 3)
+    rm, rv = rm0.clone(), rv0.clone()
+    y, mean, rstd = F.stem_conv_fwd_bnstats(x4, w2, rm, rv)
+    assert torch.equal(y, _shifted_copy(x4, tap, ch, 64, 7, 7, 2, 3)), "stem y is not the shifted copy"
+    m = y.numel() // 64
+    yd = y.reshape(m, 64).double()
+    _check_exact(yd, yd * yd)
+    _assert_stats(mean, rstd, rm, rv, rm0, rv0, yd.sum(0), (yd * yd).sum(0), m, "stem")
+
+
+@pytest.mark.parametrize("dtype", [BF, HF], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("n, w", [(2000, 121), (4000, 100)])
+def test_colstats_h1_partial_buffer(cuda, n, w, dtype):
+    """3 x 3 stride-1 convolutions of height 1: the halo kernel would write ceil(N 2 (W + 2) / 256) partial rows, more than the
+    ceil(M / 128) the documented contract asks the caller for.  colstats must hand the launch to the tile kernel."""
+    lib = C.lib()
+    m = n * w
+    assert lib.dle_conv3x3_tiles(n, 1, w) > max((m + 127) // 128, min(1032, (m + 63) // 64 + 8))
+    x = _grid((n, 1, w, 64), n + w, dtype, cuda)
+    wt, tap, ch = _onehot_weight(64, 3, 3, 64, dtype, cuda)
+    y, groups, mean, rstd = _colstats(x, wt, 1, 1, None, None)
+    assert groups == (m + 127) // 128
+    assert torch.equal(y, _shifted_copy(x, tap, ch, 64, 3, 3, 1, 1))
+    yd = y.reshape(m, 64).double()
+    _check_exact(yd, yd * yd)
+    _assert_stats(mean, rstd, None, None, None, None, yd.sum(0), (yd * yd).sum(0), m, "H=1")
+    y2, mean2, rstd2 = F.conv2d_fwd_bnstats(x, wt, 1, 1)
+    assert torch.equal(y2, y) and torch.equal(mean2, mean) and torch.equal(rstd2, rstd)
+
+
+# ---------------------------------------------------------------- forward apply
+TAIL = 4096          # elements past M C in the output buffers (512 mask bytes)
+SENT16 = -13.5       # sentinel of the 16-bit outputs (exact in both types)
+SENT8 = 0xA5
+
+
+def _apply(x, res, mean, rstd, gamma, beta, relu, want_mask):
+    m, c = x.shape
+    ybuf = torch.full((m * c + TAIL,), SENT16, dtype=x.dtype, device=x.device)
+    mbuf = torch.full((m * c // 8 + TAIL // 8,), SENT8, dtype=torch.uint8, device=x.device) if want_mask else None
+    C.call("dle_bn_fwd_apply", C.ptr(x), C.ptr(res), C.ptr(ybuf), C.ptr(mbuf), C.ptr(mean), C.ptr(rstd), C.ptr(gamma), C.ptr(beta), m, c,
+           int(relu), C.dt(x), C.stream())
+    assert bool((ybuf[m * c:] == SENT16).all()), "bn_fwd_apply wrote past M C"
+    if mbuf is not None:
+        assert bool((mbuf[m * c // 8:] == SENT8).all()), "bn_fwd_apply wrote keep bits past M C / 8"
+    return ybuf[:m * c].view(m, c), mbuf
+
+
+def _affine(c, dev, seed):
+    g = _gen(dev, seed)
+    mean = torch.randn(c, generator=g, device=dev) * 0.5
+    rstd = torch.rand(c, generator=g, device=dev) * 1.5 + 0.5
+    gamma = torch.rand(c, generator=g, device=dev) + 0.5
+    beta = torch.randn(c, generator=g, device=dev) * 0.2
+    return mean, rstd, gamma, beta
+
+
+def _assert_apply(y, x, res, mean, rstd, gamma, beta, relu, what):
+    xd, md, sd, gd, bd = x.double(), mean.double(), rstd.double(), gamma.double(), beta.double()
+    sc = sd * gd
+    ref = (xd - md) * sc + bd
+    noise = (xd * sc).abs() + (md * sc).abs() + bd.abs()
+    if res is not None:
+        ref = ref + res.double()
+        noise = noise + res.double().abs()
+    if relu:
+        ref = ref.clamp_min(0.0)
+    noise = 6 * U * noise
+    ref16 = ref.to(y.dtype).double()
+    got = y.double()
+    bar = _ulp16(torch.maximum(got.abs(), ref16.abs()), y.dtype) + noise + 2 * U * ref.abs()
+    d = (got - ref16).abs()
+    assert bool((d <= bar).all()), "%s: worst %g of the bar at %s" % (what, float((d / bar).max()), torch.nonzero(d > bar)[:4].tolist())
+
+
+APPLY_VARIANTS = [("res_relu_bits", True, True, True), ("relu_bits", False, True, True), ("relu", False, True, False),
+                  ("res_plain", True, False, False), ("plain", False, False, False)]
+APPLY_CASES = [case + v for case in CASES for v in APPLY_VARIANTS if case[0] == BF or v[0] in ("res_relu_bits", "plain")]
+
+
+@pytest.mark.parametrize("dtype, m, c, vid, has_res, relu, bits", APPLY_CASES,
+                         ids=["%s-%s" % (i, v[0]) for i, case in zip(CASE_IDS, CASES) for v in APPLY_VARIANTS
+                              if case[0] == BF or v[0] in ("res_relu_bits", "plain")])
+def test_fwd_apply(cuda, dtype, m, c, vid, has_res, relu, bits):
+    g = _gen(cuda, 3 * m + c)
+    x = (torch.randn((m, c), generator=g, device=cuda) * 1.5 + 0.3).to(dtype)
+    res = torch.randn((m, c), generator=g, device=cuda).to(dtype) if has_res else None
+    mean, rstd, gamma, beta = _affine(c, cuda, c)
+    y, mask = _apply(x, res, mean, rstd, gamma, beta, relu, bits)
+    _assert_apply(y, x, res, mean, rstd, gamma, beta, relu, "%s M=%d C=%d" % (vid, m, c))
+    if bits:
+        assert torch.equal(_unpack_bits(mask, m * c), (y > 0).reshape(-1)), "keep bits != y > 0"
+
+
+APPLY2_CASES = [(BF, 802816, 256), (BF, 200704, 512), (BF, 50176, 1024), (BF, 12544, 2048), (BF, 150089, 72), (HF, 50176, 1024)]
+
+
+@pytest.mark.parametrize("dtype, m, c", APPLY2_CASES,
+                         ids=["%s-%dx%d" % ("bf16" if d == BF else "fp16", m, c) for d, m, c in APPLY2_CASES])
+def test_fwd_apply2(cuda, dtype, m, c):
+    """bn_fwd_apply(..., residual_bn=): the downsample branch's BatchNorm on the residual's load, bit-identical to the stand-alone
+    apply of that branch (no ReLU) followed by the residual apply, which test_fwd_apply holds to the reference."""
+    g = _gen(cuda, 5 * m + c)
+    x = (torch.randn((m, c), generator=g, device=cuda) * 1.5 + 0.3).to(dtype)
+    xr = (torch.randn((m, c), generator=g, device=cuda) - 0.2).to(dtype)
+    mean, rstd, gamma, beta = _affine(c, cuda, c)
+    bn_r = _affine(c, cuda, c + 1)
+    y2, mask2 = F.bn_fwd_apply(x, mean, rstd, gamma, beta, residual=xr, relu=True, want_mask=True, residual_bn=bn_r)
+    r16, _ = _apply(xr, None, *bn_r, False, False)
+    _assert_apply(r16, xr, None, *bn_r, False, "branch")
+    y, mask = _apply(x, r16, mean, rstd, gamma, beta, True, True)
+    assert torch.equal(y2.view(m, c), y) and torch.equal(mask2, mask[:m * c // 8])
+
+
+# ---------------------------------------------------------------- backward
+def _bwd_inputs(dtype, m, c, dev, relu):
+    x = _grid((m, c), m + 2 * c, dtype, dev)
+    dy = _grid((m, c), m + 3 * c, dtype, dev)
+    keep = torch.rand((m, c), generator=_gen(dev, m + 4 * c), device=dev) < 0.6 if relu else torch.ones((m, c), dtype=torch.bool,
+                                                                                                            device=dev)
+    mean = torch.zeros(c, device=dev)
+    rstd = 2.0 ** (torch.arange(c, device=dev) % 2).float()              # 1 or 2: g xhat stays on the 1/16 grid
+    gamma = torch.rand(c, generator=_gen(dev, c), device=dev) + 0.5
+    return x, dy, keep, mean, rstd, gamma
+
+
+def _bwd_reduce(dy, y, mask, x, mean, rstd, dgamma, dbeta, accumulate):
+    m, c = x.shape
+    nbytes = int(C.lib().dle_bn_workspace_bytes(m, c))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    C.call("dle_bn_bwd_reduce", C.ptr(dy), C.ptr(y), C.ptr(mask), C.ptr(x), C.ptr(mean), C.ptr(rstd), C.ptr(dgamma), C.ptr(dbeta), m, c,
+           int(accumulate), C.ptr(ws), nbytes, C.dt(x), C.stream())
+
+
+BWD_MODES = ["mask", "saved_y", "no_relu"]
+BWD_CASES = [case + (mm,) for case in CASES for mm in BWD_MODES if case[0] == BF or mm != "saved_y"]
+
+
+@pytest.mark.parametrize("dtype, m, c, mm", BWD_CASES,
+                         ids=["%s-%s" % (i, mm) for i, case in zip(CASE_IDS, CASES) for mm in BWD_MODES if case[0] == BF or mm != "saved_y"])
+def test_bwd(cuda, dtype, m, c, mm):
+    """bn_bwd's two passes: the reduction (MM 1 bit mask, MM 2 saved y, MM 0 no ReLU) bit-exact on exactly summable inputs, the
+    apply pass against the float64 formula, g_out = dy keep bit for bit; dle_bn_bwd_reduce with accumulate=1 doubles the sums."""
+    x, dy, keep, mean, rstd, gamma = _bwd_inputs(dtype, m, c, cuda, mm != "no_relu")
+    y = mask = None
+    if mm == "saved_y":
+        y = torch.where(keep, x.abs() + 0.25, torch.zeros((), dtype=dtype, device=cuda))
+    elif mm == "mask":
+        mask = _pack_bits(keep)
+    dgamma = torch.full((c,), float("nan"), device=cuda)
+    dbeta = torch.full((c,), float("nan"), device=cuda)
+    _bwd_reduce(dy, y, mask, x, mean, rstd, dgamma, dbeta, 0)
+    gd = torch.where(keep, dy.double(), torch.zeros((), dtype=torch.float64, device=cuda))
+    xhat = x.double() * rstd.double()
+    _check_exact(gd, gd * xhat)
+    ref_dbeta, ref_dgamma = gd.sum(0), (gd * xhat).sum(0)
+    assert torch.equal(dbeta, ref_dbeta.float()), "dbeta at %s" % torch.nonzero(dbeta != ref_dbeta.float())[:4].tolist()
+    assert torch.equal(dgamma, ref_dgamma.float()), "dgamma at %s" % torch.nonzero(dgamma != ref_dgamma.float())[:4].tolist()
+    dxbuf = torch.full((m * c + TAIL,), SENT16, dtype=dtype, device=cuda)
+    gbuf = torch.full((m * c + TAIL,), SENT16, dtype=dtype, device=cuda)
+    C.call("dle_bn_bwd_apply", C.ptr(dy), C.ptr(y), C.ptr(mask), C.ptr(x), C.ptr(dxbuf), C.ptr(gbuf), C.ptr(mean), C.ptr(rstd),
+           C.ptr(gamma), C.ptr(dgamma), C.ptr(dbeta), m, c, C.dt(x), C.stream())
+    assert bool((dxbuf[m * c:] == SENT16).all()) and bool((gbuf[m * c:] == SENT16).all()), "bn_bwd_apply wrote past M C"
+    assert torch.equal(gbuf[:m * c].view(m, c), gd.to(dtype)), "g_out != dy keep"
+    ref_dx = gamma.double() * rstd.double() * (gd - ref_dbeta / m - xhat * (ref_dgamma / m))
+    err = float((dxbuf[:m * c].view(m, c).double() - ref_dx).abs().max())
+    assert err <= 1.5 * STEP[dtype] * float(ref_dx.abs().max()), "dx error %g" % err
+    dx2, g2 = F.bn_bwd(dy, y, x, mean, rstd, gamma, dgamma, dbeta, want_skip_grad=True, relu_mask=mask, reduce_done=True)
+    assert torch.equal(dx2, dxbuf[:m * c].view(m, c)) and torch.equal(g2, gbuf[:m * c].view(m, c))
+    if mm == "mask":
+        _bwd_reduce(dy, y, mask, x, mean, rstd, dgamma, dbeta, 1)
+        assert torch.equal(dbeta, (2 * ref_dbeta).float()) and torch.equal(dgamma, (2 * ref_dgamma).float()), "accumulate=1"
+
+
+@pytest.mark.parametrize("c", [64, 520, 2048])
+@pytest.mark.parametrize("groups", [1, 33, 392, 1032])
+def test_bwd_finish_accumulate(cuda, groups, c):
+    """dle_bn_bwd_finish on partial rows left by another kernel, with accumulate=1 on top of non-zero dgamma / dbeta."""
+    g = _gen(cuda, 10 * groups + c)
+    s0 = torch.randint(-256, 257, (groups, c), generator=g, device=cuda).double() / 16
+    s1 = torch.randint(-256, 257, (groups, c), generator=g, device=cuda).double() / 16
+    _check_exact(s0, s1)
+    part = torch.stack([s0, s1], 1).float().contiguous()
+    db0 = torch.randint(-64, 65, (c,), generator=g, device=cuda).float() / 16
+    dg0 = torch.randint(-64, 65, (c,), generator=g, device=cuda).float() / 16
+    dbeta, dgamma = db0.clone(), dg0.clone()
+    C.call("dle_bn_bwd_finish", C.ptr(part), groups, c, C.ptr(dgamma), C.ptr(dbeta), 1, C.stream())
+    assert torch.equal(dbeta, (db0.double() + s0.sum(0)).float()) and torch.equal(dgamma, (dg0.double() + s1.sum(0)).float())
+    C.call("dle_bn_bwd_finish", C.ptr(part), groups, c, C.ptr(dgamma), C.ptr(dbeta), 0, C.stream())
+    assert torch.equal(dbeta, s0.sum(0).float()) and torch.equal(dgamma, s1.sum(0).float())
