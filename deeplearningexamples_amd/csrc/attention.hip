@@ -913,29 +913,19 @@ static int attention_bwd_impl(const void* qkv, const void* dctx, const float* ma
   a.drop = make_drop(nullptr, p, seed, offset, offset_base);
   a.S = S; a.nblk = S / AT_S; a.sw = dle_attention_stats_floats(S);
   const size_t lds = 4 * AT_TILE * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<DLE_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<DLE_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_long_kernel<DLE_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_long_kernel<DLE_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_long_kernel<DLE_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + AT_S * AT_S * 2));
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_long_kernel<DLE_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + AT_S * AT_S * 2));
-    attr_set = true;
-  }
-  if (S != AT_S) {
-    // (1) per query block: delta into the statistics rows, dQ; (2) per key block: dK, dV (reads the deltas: stream order)
-    const dim3 grid(B * heads * a.nblk);
-    if (dtype == DLE_F16) hipLaunchKernelGGL(attn_bwd_dq_long_kernel<DLE_F16>, grid, dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_long_kernel<DLE_BF16>, grid, dim3(256), lds, stream, a);
-    DLE_LAUNCH_CHECK();
-    if (dtype == DLE_F16) hipLaunchKernelGGL(attn_bwd_dkv_long_kernel<DLE_F16>, grid, dim3(256), lds + AT_S * AT_S * 2, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dkv_long_kernel<DLE_BF16>, grid, dim3(256), lds + AT_S * AT_S * 2, stream, a);
+  if (S == AT_S) {
+    if (dtype == DLE_F16) DLE_LAUNCH_LDS(attn_bwd_kernel<DLE_F16>, dim3(B * heads), dim3(256), lds, stream, a);
+    else DLE_LAUNCH_LDS(attn_bwd_kernel<DLE_BF16>, dim3(B * heads), dim3(256), lds, stream, a);
     DLE_LAUNCH_CHECK();
     return 0;
   }
-  if (dtype == DLE_F16) hipLaunchKernelGGL(attn_bwd_kernel<DLE_F16>, dim3(B * heads), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL(attn_bwd_kernel<DLE_BF16>, dim3(B * heads), dim3(256), lds, stream, a);
+  // (1) per query block: delta into the statistics rows, dQ; (2) per key block: dK, dV (reads the deltas: stream order)
+  const dim3 grid(B * heads * a.nblk);
+  if (dtype == DLE_F16) DLE_LAUNCH_LDS(attn_bwd_dq_long_kernel<DLE_F16>, grid, dim3(256), lds, stream, a);
+  else DLE_LAUNCH_LDS(attn_bwd_dq_long_kernel<DLE_BF16>, grid, dim3(256), lds, stream, a);
+  DLE_LAUNCH_CHECK();
+  if (dtype == DLE_F16) DLE_LAUNCH_LDS(attn_bwd_dkv_long_kernel<DLE_F16>, grid, dim3(256), lds + AT_S * AT_S * 2, stream, a);
+  else DLE_LAUNCH_LDS(attn_bwd_dkv_long_kernel<DLE_BF16>, grid, dim3(256), lds + AT_S * AT_S * 2, stream, a);
   DLE_LAUNCH_CHECK();
   return 0;
 }

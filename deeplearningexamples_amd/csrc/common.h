@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <mutex>
 
 #define DLE_WAVE 64
 
@@ -37,6 +39,55 @@ extern "C" void dle_set_error(const char* fmt, ...);
       dle_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e__)); \
       return (int)e__;                                            \
     }                                                             \
+  } while (0)
+
+// ---- per-device host state (inline: one instance of each static across the library) ------------------------------
+#define DLE_MAX_DEVICES 64
+
+// current device index, or -1 when hipGetDevice fails or the index is out of range
+inline int dle_current_device() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DLE_MAX_DEVICES) return -1;
+  return dev;
+}
+
+struct DleDeviceLimits { int cus, lds_per_block; };
+// the current device's CU count (256 when the query returns 0) and MaxSharedMemoryPerBlock, queried once per device;
+// nullptr when the device index is unusable
+inline const DleDeviceLimits* dle_device_limits() {
+  static std::once_flag once[DLE_MAX_DEVICES];
+  static DleDeviceLimits lim[DLE_MAX_DEVICES];
+  const int dev = dle_current_device();
+  if (dev < 0) return nullptr;
+  std::call_once(once[dev], [dev] {
+    int cus = 0, lds = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    lim[dev] = {cus > 0 ? cus : 256, lds};
+  });
+  return &lim[dev];
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only: set_of[dev] holds the largest
+// size set so far for this kernel on device dev.  Raising it is serialised so that a smaller concurrent request never
+// lowers the attribute below a recorded size.  Its return is ignored: a launch it would fail reports through
+// hipGetLastError.
+inline void dle_lds_opt_in(const void* kernel, std::atomic<int>* set_of, int bytes) {
+  const int dev = dle_current_device();
+  if (dev >= 0 && set_of[dev].load(std::memory_order_acquire) >= bytes) return;
+  static std::mutex raise;
+  std::lock_guard<std::mutex> lock(raise);
+  if (dev >= 0 && set_of[dev].load(std::memory_order_relaxed) >= bytes) return;
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (dev >= 0) set_of[dev].store(bytes, std::memory_order_release);
+}
+
+// hipLaunchKernelGGL with `lds` bytes of dynamic LDS, opted in first (a kernel template-id goes in parentheses)
+#define DLE_LAUNCH_LDS(kernel, grid, block, lds, stream, ...)                      \
+  do {                                                                            \
+    static std::atomic<int> dle_lds_set_[DLE_MAX_DEVICES];                        \
+    dle_lds_opt_in((const void*)kernel, dle_lds_set_, (int)(lds));               \
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);            \
   } while (0)
 
 // ---- 16-bit float <-> f32 bit helpers (storage type = unsigned short) -------------

@@ -273,9 +273,7 @@ extern "C" int dle_conv3x3_try(const void* x, const void* w, void* y, float* sta
     return 2;
   }
   dim3 grid((unsigned)(p.tiles_m * p.tiles_n)), block(256);
-#define C3_GO(DT, DG, NTV) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3x3_kernel<DT, DG, NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr_set = true; } \
-    hipLaunchKernelGGL((conv3x3_kernel<DT, DG, NTV>), grid, block, lds, stream, p); } while (0)
+#define C3_GO(DT, DG, NTV) DLE_LAUNCH_LDS((conv3x3_kernel<DT, DG, NTV>), grid, block, lds, stream, p)
 #define C3_PICK(DT) do { if (dgrad) { if (NT == 128) C3_GO(DT, true, 128); else C3_GO(DT, true, 64); } \
                          else { if (NT == 128) C3_GO(DT, false, 128); else C3_GO(DT, false, 64); } } while (0)
   if (dtype == DLE_F16) C3_PICK(DLE_F16); else C3_PICK(DLE_BF16);

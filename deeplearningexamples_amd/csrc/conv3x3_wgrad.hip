@@ -278,9 +278,7 @@ extern "C" int dle_conv3x3_wgrad_try(const void* dy, const void* x, float* dw, i
   if (lds < 4 * 5 * 16 * 64 * 4) lds = 4 * 5 * 16 * 64 * 4;          // the meeting buffer of the pixel halves (80 KiB)
   if (lds > 160 * 1024 || p.ppieces > 32) return 0;
   const dim3 grid(256), block(512);
-#define W3_GO(DT) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; } \
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<DT>), grid, block, lds, stream, p); } while (0)
+#define W3_GO(DT) DLE_LAUNCH_LDS((conv3x3_wgrad_kernel<DT>), grid, block, lds, stream, p)
   if (dtype == DLE_F16) W3_GO(DLE_F16); else W3_GO(DLE_BF16);
 #undef W3_GO
   hipError_t e = hipGetLastError();

@@ -281,9 +281,7 @@ extern "C" int dle_conv1x1_bnbwd_dgrad(const void* dy, const void* t, const void
   if (bred && partial_bytes < (long long)groups * 2 * N * 4) return 0;
   const size_t lds = (size_t)N * (K + BB_PAD) * 2 + 5 * K * 4 + 2 * N * 4;
   const dim3 grid((unsigned)groups), block(NWv * 64);
-#define BB_GO(DT, MK, BR) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_bnbwd_kernel<DT, 8, 4, NWv, MK, BR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); attr_set = true; } \
-    hipLaunchKernelGGL((conv_bnbwd_kernel<DT, 8, 4, NWv, MK, BR>), grid, block, lds, stream, p); } while (0)
+#define BB_GO(DT, MK, BR) DLE_LAUNCH_LDS((conv_bnbwd_kernel<DT, 8, 4, NWv, MK, BR>), grid, block, lds, stream, p)
 #define BB_M(DT) do { if (relu_mask) { if (bred) BB_GO(DT, true, true); else BB_GO(DT, true, false); } \
                       else { if (bred) BB_GO(DT, false, true); else BB_GO(DT, false, false); } } while (0)
   if (dtype == DLE_F16) BB_M(DLE_F16); else BB_M(DLE_BF16);

@@ -279,9 +279,7 @@ static int bnload_launch(const void* t, const void* res, const void* w, void* ou
   size_t lds = (size_t)TN * (K + BL_PAD) * 2 + 4 * K * 4;
   if (lds < (size_t)NWv * 2 * TN * 4) lds = (size_t)NWv * 2 * TN * 4;
   const dim3 grid((unsigned)(groups * p.col_tiles)), block(NWv * 64);
-#define BL_GO(DT, KS, RS, NBV, NWV) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_bnload_kernel<DT, KS, RS, NBV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024); attr_set = true; } \
-    hipLaunchKernelGGL((conv_bnload_kernel<DT, KS, RS, NBV, NWV>), grid, block, lds, stream, p); } while (0)
+#define BL_GO(DT, KS, RS, NBV, NWV) DLE_LAUNCH_LDS((conv_bnload_kernel<DT, KS, RS, NBV, NWV>), grid, block, lds, stream, p)
 #define BL_NB(DT, KS, RS, NWV) do { if (TN == 128) BL_GO(DT, KS, RS, 8, NWV); else BL_GO(DT, KS, RS, 4, NWV); } while (0)
 #define BL_RES(DT, KS, NWV) do { if (resmode == 2) BL_NB(DT, KS, 2, NWV); else if (resmode == 1) BL_NB(DT, KS, 1, NWV); else BL_NB(DT, KS, 0, NWV); } while (0)
 #define BL_K(DT) do { if (K == 64) BL_RES(DT, 2, 4); else if (K == 128) BL_RES(DT, 4, 4); else if (K == 512) BL_GO(DT, 16, 1, 8, 8); \

@@ -235,12 +235,7 @@ static bool oh_envelope(OhArgs& p, float* weight, const int64_t* rows, const voi
 // the segment-sum kernel alone: partial blocks ws[k][slice][row < nrows[k]][128]; 0 or a launch error + 1000
 static int oh_launch_partials(const OhArgs& p, int grad_dtype, hipStream_t stream) {
   const size_t lds = 64 * 1024;                                          // 2 x 16 KiB tiles + ids; the meeting buffer of the halves
-#define GO(DT)                                                                                                           \
-  do {                                                                                                                   \
-    static bool attr_set = false;                                                                                        \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)emb_onehot_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
-    hipLaunchKernelGGL((emb_onehot_kernel<DT>), dim3(p.n * p.slices), dim3(512), lds, stream, p);                        \
-  } while (0)
+#define GO(DT) DLE_LAUNCH_LDS((emb_onehot_kernel<DT>), dim3(p.n * p.slices), dim3(512), lds, stream, p)
   if (grad_dtype == DLE_F16) GO(DLE_F16); else GO(DLE_BF16);
 #undef GO
   hipError_t e = hipGetLastError();

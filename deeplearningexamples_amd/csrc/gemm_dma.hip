@@ -795,23 +795,20 @@ static int launch_gemm(const Gemm2Args& p_in, int in_dtype, int amode, int bmode
   const long long work_big = tiles_big * (batch > 0 ? batch : 1) * (SLAB_MODE(p) ? p.splitk : 1);
   const bool want = !p.force_small && (big_mode >= 1 || (big_mode != 0 && (p.splitk == 1 || SLAB_MODE(p)) && kt_per_item >= 4 &&
                                                          work_big >= (p.splitk == 1 ? 160 : 128)));
-  if (tile_rows_out) *tile_rows_out = (fits && want) ? 256 : BM;
-  if (fits && want) {
+  // (an unusable device index declines the big tile)
+  const DleDeviceLimits* lim = fits && want ? dle_device_limits() : nullptr;
+  if (tile_rows_out) *tile_rows_out = lim ? 256 : BM;
+  if (lim) {
     dim3 grid((unsigned)tiles_big, p.splitk, batch > 0 ? batch : 1), block(512);
     // 128 KiB of operand stages + (when the device grants a workgroup the whole 160 KiB) 32 KiB for epilogue source rows
-    static const int lds_max = [] { int dev = 0, v = 0; hipGetDevice(&dev);
-                                    hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev); return v; }();
+    const int lds_max = lim->lds_per_block;
     static const int lds_src_mode = getenv("DLE_GEMM_LDS_SRC") ? atoi(getenv("DLE_GEMM_LDS_SRC")) : 1;
     const size_t lds_stages = 2 * (256 * BK + 256 * BK) * 2;
     p.lds_src = lds_src_mode && lds_max >= (int)(lds_stages + 32768) && (long long)p.M * p.ldc * 2 < 0xFFFFFFE0LL;
     const size_t lds_big = lds_stages + (lds_max >= (int)(lds_stages + 32768) ? 32768 : 0);
-#define GOBIG(DT, AM, BMODE) do { static bool attr_set = false; \
-      if (!attr_set) { hipFuncSetAttribute((const void*)gemm2_kernel<DT, AM, BMODE, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big); attr_set = true; } \
-      hipLaunchKernelGGL((gemm2_kernel<DT, AM, BMODE, 2, 1>), grid, block, lds_big, stream, p); } while (0)
+#define GOBIG(DT, AM, BMODE) DLE_LAUNCH_LDS((gemm2_kernel<DT, AM, BMODE, 2, 1>), grid, block, lds_big, stream, p)
 #define PICKBIG(DT) do { if (amode == 0 && bmode == 0) GOBIG(DT, 0, 0); else if (amode == 0) GOBIG(DT, 0, 1); else GOBIG(DT, 1, 1); } while (0)
-#define GOBIGST(DT) do { static bool attr_set = false; \
-      if (!attr_set) { hipFuncSetAttribute((const void*)gemm2_kernel<DT, 0, 1, 2, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big); attr_set = true; } \
-      hipLaunchKernelGGL((gemm2_kernel<DT, 0, 1, 2, 1, 0, 1>), grid, block, lds_big, stream, p); } while (0)
+#define GOBIGST(DT) DLE_LAUNCH_LDS((gemm2_kernel<DT, 0, 1, 2, 1, 0, 1>), grid, block, lds_big, stream, p)
     if (p.stats) {                                   // (launch_gemm's caller checked: sums only, ReLU-mask epilogue, operands (0, 1))
       if (in_dtype == DLE_F16) GOBIGST(DLE_F16); else GOBIGST(DLE_BF16);
     } else if (in_dtype == DLE_F16) PICKBIG(DLE_F16); else PICKBIG(DLE_BF16);

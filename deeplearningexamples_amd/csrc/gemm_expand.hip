@@ -373,13 +373,7 @@ extern "C" int dle_gemm_expand_try(const void* A, const void* B, void* C, const 
 #define GO(DT, KS, ACT, ST)                                                                                              \
   do {                                                                                                                   \
     constexpr int NW_ = KS > 4 ? 8 : 4;                                                                                  \
-    static bool attr_set = false;                                                                                        \
-    if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)gemm_expand_kernel<DT, KS, ACT, ST, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                EX_TN * (KS * 32 + EX_PAD) * 2);                                                         \
-      attr_set = true;                                                                                                   \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((gemm_expand_kernel<DT, KS, ACT, ST, NW_>), grid, block, lds_bytes, stream, p);                   \
+    DLE_LAUNCH_LDS((gemm_expand_kernel<DT, KS, ACT, ST, NW_>), grid, block, lds_bytes, stream, p);                       \
   } while (0)
 #define PICK_ACT(DT, KS)                                              \
   do {                                                                \
@@ -438,13 +432,7 @@ extern "C" int dle_gemm_expand_masked_bnred(const void* A, const void* B, void* 
 #define GO(DT, KS)                                                                                                       \
   do {                                                                                                                   \
     constexpr int NW_ = KS > 4 ? 8 : 4;                                                                                  \
-    static bool attr_set = false;                                                                                        \
-    if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)gemm_expand_kernel<DT, KS, 2, false, NW_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                EX_TN * (KS * 32 + EX_PAD) * 2 + 2 * EX_TN * 4);                                         \
-      attr_set = true;                                                                                                   \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((gemm_expand_kernel<DT, KS, 2, false, NW_, true>), grid, block, lds_bytes, stream, p);            \
+    DLE_LAUNCH_LDS((gemm_expand_kernel<DT, KS, 2, false, NW_, true>), grid, block, lds_bytes, stream, p);                \
   } while (0)
 #define PICK_K(DT) do { if (K == 64) GO(DT, 2); else if (K == 128) GO(DT, 4); else GO(DT, 8); } while (0)
   if (dtype == DLE_F16) PICK_K(DLE_F16); else PICK_K(DLE_BF16);
@@ -481,13 +469,7 @@ extern "C" int dle_gemm_expand_add_up2(const void* A, const void* B, void* C, co
 #define GO3(DT, KS)                                                                                                      \
   do {                                                                                                                   \
     constexpr int NW_ = KS > 4 ? 8 : 4;                                                                                  \
-    static bool attr_set = false;                                                                                        \
-    if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)gemm_expand_kernel<DT, KS, 3, false, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                EX_TN * (KS * 32 + EX_PAD) * 2);                                                         \
-      attr_set = true;                                                                                                   \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((gemm_expand_kernel<DT, KS, 3, false, NW_>), grid, block, lds_bytes, stream, p);                  \
+    DLE_LAUNCH_LDS((gemm_expand_kernel<DT, KS, 3, false, NW_>), grid, block, lds_bytes, stream, p);                      \
   } while (0)
 #define PICK3(DT) do { if (K == 64) GO3(DT, 2); else if (K == 128) GO3(DT, 4); else GO3(DT, 8); } while (0)
   if (dtype == DLE_F16) PICK3(DLE_F16); else PICK3(DLE_BF16);

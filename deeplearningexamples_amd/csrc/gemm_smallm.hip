@@ -299,12 +299,7 @@ extern "C" int dle_gemm_smallm_try(const void* A, const void* B, void* C, const 
 #define GO(DT, TN, NW, NST)                                                                                                    \
   do {                                                                                                                         \
     constexpr int lds_bytes = NST * (SM_TS + TN) * SM_BKE * 2;                                                                 \
-    static bool attr_set = false;                                                                                              \
-    if (!attr_set) {                                                                                                           \
-      (void)hipFuncSetAttribute((const void*)gemm_smallm_kernel<DT, TN, NW, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-      attr_set = true;                                                                                                         \
-    }                                                                                                                          \
-    hipLaunchKernelGGL((gemm_smallm_kernel<DT, TN, NW, NST>), dim3(tiles), dim3(NW * 64), lds_bytes, stream, p);               \
+    DLE_LAUNCH_LDS((gemm_smallm_kernel<DT, TN, NW, NST>), dim3(tiles), dim3(NW * 64), lds_bytes, stream, p);                   \
   } while (0)
 #define PICK(DT)                                                            \
   do {                                                                      \
@@ -350,12 +345,7 @@ extern "C" int dle_t2_lstm_gemm_fwd(const void* x, int64_t ldx, const void* w, i
 #define GOL(DT, NST)                                                                                                          \
   do {                                                                                                                         \
     constexpr int lds_bytes = NST * (SM_TS + 32) * SM_BKE * 2;                                                                 \
-    static bool attr_set = false;                                                                                              \
-    if (!attr_set) {                                                                                                           \
-      (void)hipFuncSetAttribute((const void*)gemm_smallm_kernel<DT, 32, 8, NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-      attr_set = true;                                                                                                         \
-    }                                                                                                                          \
-    hipLaunchKernelGGL((gemm_smallm_kernel<DT, 32, 8, NST, true>), dim3(tiles), dim3(512), lds_bytes, stream, p);              \
+    DLE_LAUNCH_LDS((gemm_smallm_kernel<DT, 32, 8, NST, true>), dim3(tiles), dim3(512), lds_bytes, stream, p);                  \
   } while (0)
   if (dtype == DLE_F16) { if (deep) GOL(DLE_F16, 4); else GOL(DLE_F16, 3); }
   else { if (deep) GOL(DLE_BF16, 4); else GOL(DLE_BF16, 3); }

@@ -692,18 +692,11 @@ extern "C" int dle_t2_attention_fwd(const float* q, const void* pl, const float*
   DLE_CHECK_ARG(lds <= 160 * 1024, "t2_attention_fwd: Ti too large for one workgroup's LDS");
   const int lpa = t2_pow2_ge(A / 8), lpe = t2_pow2_ge(E / 8);
 #define T2_ATT_FWD(DT)                                                                                                              \
-  do {                                                                                                                              \
-    static size_t lds_set = 0;                                                                                                      \
-    if (lds > 65536 && lds > lds_set) {                                                                                             \
-      (void)hipFuncSetAttribute((const void*)t2_attention_fwd_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-      lds_set = lds;                                                                                                                \
-    }                                                                                                                               \
-    hipLaunchKernelGGL(t2_attention_fwd_kernel<DT>, dim3(B), dim3(T2A_BLOCK), lds, stream, q, (const unsigned short*)pl, v,         \
-                       (const unsigned short*)memory, (const long long*)lengths, (const unsigned short*)awc_prev,                   \
-                       (unsigned short*)tanh_out, aw_out, (unsigned short*)awc_next, (unsigned short*)d0, (long long)ld0,           \
-                       (unsigned short*)d1, (long long)ld1, (unsigned short*)d2, (long long)ld2, Ti, A, E, lpa, lpe,                \
-                       (const unsigned short*)wloc, KL, KK);                                                                        \
-  } while (0)
+    DLE_LAUNCH_LDS(t2_attention_fwd_kernel<DT>, dim3(B), dim3(T2A_BLOCK), lds, stream, q, (const unsigned short*)pl, v,             \
+                   (const unsigned short*)memory, (const long long*)lengths, (const unsigned short*)awc_prev,                       \
+                   (unsigned short*)tanh_out, aw_out, (unsigned short*)awc_next, (unsigned short*)d0, (long long)ld0,               \
+                   (unsigned short*)d1, (long long)ld1, (unsigned short*)d2, (long long)ld2, Ti, A, E, lpa, lpe,                    \
+                   (const unsigned short*)wloc, KL, KK)
   if (dtype == DLE_F16) T2_ATT_FWD(DLE_F16); else T2_ATT_FWD(DLE_BF16);
 #undef T2_ATT_FWD
   DLE_LAUNCH_CHECK();
@@ -732,18 +725,11 @@ extern "C" int dle_t2_attention_bwd(const float* d_ctx0, int64_t ld_c0, const fl
   T2_DT_CHECK("t2_attention_bwd");
   const int lpa = t2_pow2_ge(A / 8), lpe = t2_pow2_ge(E / 8);
 #define T2_ATT_BWD(DT)                                                                                                              \
-  do {                                                                                                                              \
-    static size_t lds_set = 0;                                                                                                      \
-    if (lds > 65536 && lds > lds_set) {                                                                                             \
-      (void)hipFuncSetAttribute((const void*)t2_attention_bwd_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-      lds_set = lds;                                                                                                                \
-    }                                                                                                                               \
-    hipLaunchKernelGGL(t2_attention_bwd_kernel<DT>, dim3(B), dim3(T2A_BLOCK), lds, stream, d_ctx0, (long long)ld_c0, d_ctx1,        \
-                       (long long)ld_c1, d_ctx2, (long long)ld_c2, d_aw0, d_aw1, aw, (const unsigned short*)tanh_out, v,            \
-                       (const unsigned short*)memory, d_memory, (unsigned short*)d_pl, dq, (unsigned short*)dq16,                   \
-                       (unsigned short*)dctx16, dv_acc, d_pm_acc, Ti, A, E, lpa, lpe, (const unsigned short*)wlocT, KL, KK,         \
-                       d_prev, d_cum);                                                                                              \
-  } while (0)
+    DLE_LAUNCH_LDS(t2_attention_bwd_kernel<DT>, dim3(B), dim3(T2A_BLOCK), lds, stream, d_ctx0, (long long)ld_c0, d_ctx1,            \
+                   (long long)ld_c1, d_ctx2, (long long)ld_c2, d_aw0, d_aw1, aw, (const unsigned short*)tanh_out, v,                \
+                   (const unsigned short*)memory, d_memory, (unsigned short*)d_pl, dq, (unsigned short*)dq16,                       \
+                   (unsigned short*)dctx16, dv_acc, d_pm_acc, Ti, A, E, lpa, lpe, (const unsigned short*)wlocT, KL, KK,             \
+                   d_prev, d_cum)
   if (dtype == DLE_F16) T2_ATT_BWD(DLE_F16); else T2_ATT_BWD(DLE_BF16);
 #undef T2_ATT_BWD
   DLE_LAUNCH_CHECK();

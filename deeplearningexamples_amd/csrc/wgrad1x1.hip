@@ -231,9 +231,8 @@ extern "C" int dle_wgrad1x1_try(const void* dy, const void* x, float* dw, int M,
   if (wgs > p.ntiles) wgs = p.ntiles;
   if (workspace_bytes < (long long)wgs * Ko * C * 4) return 0;
   const dim3 grid(wgs), block(512);
-#define W1_GO(DT, KOv, CCv, TGv, PHv, WGMv, WGNv, WMv, WNv) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)wgrad1x1_kernel<DT, KOv, CCv, TGv, PHv, WGMv, WGNv, WMv, WNv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; } \
-    hipLaunchKernelGGL((wgrad1x1_kernel<DT, KOv, CCv, TGv, PHv, WGMv, WGNv, WMv, WNv>), grid, block, lds, stream, p); } while (0)
+#define W1_GO(DT, KOv, CCv, TGv, PHv, WGMv, WGNv, WMv, WNv) \
+    DLE_LAUNCH_LDS((wgrad1x1_kernel<DT, KOv, CCv, TGv, PHv, WGMv, WGNv, WMv, WNv>), grid, block, lds, stream, p)
 #define W1_PICK(DT) do { \
     if (Ko == 256 && C == 64) W1_GO(DT, 256, 64, 64, 1, 8, 1, 1, 2); \
     else if (Ko == 64 && C == 256) W1_GO(DT, 64, 256, 64, 1, 2, 4, 1, 2); \
