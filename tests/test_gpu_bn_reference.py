@@ -55,6 +55,7 @@ import torch
 
 from deeplearningexamples_amd import _cabi as C
 from deeplearningexamples_amd import functional as F
+from tests._exact_grid import check_exact as _check_exact, gen as _gen, grid as _grid, ulp16 as _ulp16
 
 pytestmark = pytest.mark.gpu
 
@@ -64,8 +65,6 @@ EPS64 = float(torch.tensor(EPS, dtype=torch.float32))      # the fp32 argument a
 MOM = 0.1
 MOM32 = torch.tensor(MOM, dtype=torch.float32)
 ONE_MINUS_MOM = float(torch.tensor(1.0, dtype=torch.float32) - MOM32)   # (1.f - momentum), in fp32
-MANT = {torch.float16: 10, torch.bfloat16: 7}
-EMIN = {torch.float16: -14, torch.bfloat16: -126}
 STEP = {torch.float16: 2.0 ** -10, torch.bfloat16: 2.0 ** -7}
 BF, HF = torch.bfloat16, torch.float16
 
@@ -79,36 +78,10 @@ CASE_IDS = ["%s-%dx%d" % ("bf16" if d == BF else "fp16", m, c) for d, m, c in CA
 GROUPS = [1, 31, 32, 33, 1100, 1101, 3306, 25088]
 
 
-def _gen(dev, seed):
-    return torch.Generator(device=dev).manual_seed(seed)
-
-
-def _grid(shape, seed, dtype, dev, kmax=4):
-    """k / 4 with |k| <= kmax: exact in fp16 and bf16, squares and products of two multiples of 1/16."""
-    k = torch.randint(-kmax, kmax + 1, shape, generator=_gen(dev, seed), device=dev)
-    return (k.float() * 0.25).to(dtype)
-
-
-def _check_exact(*terms):
-    """Precondition of the bit-exact bars: every term [M, C] (float64) is a multiple of 1/16 and each column's sum of magnitudes is
-    below 2^20, so every partial sum, in any order, is a multiple of 1/16 below 2^20: at most 24 significant bits, exact in fp32."""
-    for t in terms:
-        assert torch.equal(t * 16, torch.round(t * 16)), "term off the 1/16 grid"
-        worst = float(t.abs().sum(0).max())
-        assert worst < 2.0 ** 20, "column magnitude sum %g: fp32 sums would not be exact" % worst
-
-
 def _ulp32(v):
     """fp32 spacing at |v| (v float64, normal range)."""
     _, e = torch.frexp(v.abs())
     return torch.pow(2.0, (e - 24).double())
-
-
-def _ulp16(v, dtype):
-    """Spacing of `dtype` at |v| (float64), the subnormal spacing at and near 0."""
-    _, e = torch.frexp(v.abs())
-    e = torch.where(v == 0, torch.full_like(e, EMIN[dtype] + 1), e)
-    return torch.pow(2.0, (e - 1).clamp_min(EMIN[dtype]).double() - MANT[dtype])
 
 
 def _unpack_bits(mask, n):
