@@ -87,6 +87,8 @@ class ConvBN:
         self.w2 = self.gw_flat = None
         self.wgrad_stream = None                    # set by the trainer: weight gradients run beside the data-gradient chain
         self.fuse_bnbwd = os.environ.get("DLE_RN50_FUSE_BNBWD", "1") != "0"      # BatchNorm backward on the data gradient's operand load
+        # ... and the unit's weight gradient in that kernel too: dt is never written (F.bn_bwd_conv1x1_dgrad_wgrad)
+        self.fuse_bnbwd_wgrad = os.environ.get("DLE_RN50_FUSE_BNBWD_WGRAD", "1") != "0"
         self.reduce_done = False                    # set by the unit that PRODUCED this unit's output gradient (backward(bnred=))
         self.keepalive = None                       # ... with the list that keeps their operands alive until the streams join
 
@@ -155,16 +157,25 @@ class ConvBN:
         rmask = mask if self.relu else dy_mask
         n, h, w, c = x.shape
         # conv3 / bn3 of the 56 x 56 stage: the BatchNorm backward runs on the operand load of the unit's own data gradient
-        # (csrc/conv_bnbwd.hip) -- dt is written once for the weight gradient and never read back by the data gradient
+        # (csrc/conv_bnbwd.hip) -- with the unit's weight gradient in the same kernel (dt never exists), else dt is written once
+        # for the weight gradient and never read back by the data gradient
         reduce_done, self.reduce_done = self.reduce_done, False
         fused = None
+        wgrad_done = False
         if self.fuse_bnbwd and self.k == 1 and self.stride == 1 and need_dx and dx_addend is None:   # (compact_dx: stride 2 only)
             b2 = None
             if bnred is not None and bnred.saved is not None and bnred.relu:
                 # dx of this unit is the gradient entering `bnred`'s BatchNorm (bn2 of the bottleneck): its reduction rides along
                 b2 = (bnred.saved[1], bnred.saved[2], bnred.saved[3], bnred.saved[4], bnred.ggamma, bnred.gbeta)
-            fused = F.bn_bwd_conv1x1_dgrad(dy, t, mean, rstd, self.bn.weight.data, self.ggamma, self.gbeta,
-                                           self.w16.view(self.cout, c), relu_mask=rmask, reduce_done=reduce_done, bnred=b2)
+            if self.fuse_bnbwd_wgrad and pooled is None and self.gw is not None:
+                r = F.bn_bwd_conv1x1_dgrad_wgrad(dy, t, mean, rstd, self.bn.weight.data, self.ggamma, self.gbeta,
+                                                 self.w16.view(self.cout, c), x, self.gw, relu_mask=rmask,
+                                                 reduce_done=reduce_done, bnred=b2)
+                if r is not None:
+                    fused, wgrad_done = (None, r[0], r[1]), True
+            if fused is None:
+                fused = F.bn_bwd_conv1x1_dgrad(dy, t, mean, rstd, self.bn.weight.data, self.ggamma, self.gbeta,
+                                               self.w16.view(self.cout, c), relu_mask=rmask, reduce_done=reduce_done, bnred=b2)
         gt = None
         if pooled is not None:
             if self.relu and not reduce_done:
@@ -185,13 +196,15 @@ class ConvBN:
         # The weight gradient is a leaf of the backward graph (nothing downstream reads it before the optimizer) while the data
         # gradient is on the critical chain: it goes to a second stream, where its split-K slices (one workgroup per CU, bound by
         # HBM latency rather than bandwidth) share the chip with the next unit's BatchNorm / data-gradient kernels.
-        ws = self.wgrad_stream
+        ws = self.wgrad_stream if not wgrad_done else None
         if ws is not None:
             ws.wait_stream(torch.cuda.current_stream())
             self.keepalive.append((gt, x))          # freed only after the trainer has joined the streams (no record_stream: that
                                                     # call is not capturable, and the step may be recorded into a HIP graph)
         with (torch.cuda.stream(ws) if ws is not None else _nullcontext()):
-            if c == 4:                              # stem: straight into the flat gradient of the channels_last master
+            if wgrad_done:                          # (formed on the main stream by the fused kernel)
+                pass
+            elif c == 4:                            # stem: straight into the flat gradient of the channels_last master
                 F.stem_conv_wgrad(gt, x, self.gw_flat)
             elif self.k == 1 and self.stride == 1:
                 m = n * h * w

@@ -181,6 +181,12 @@ __global__ __launch_bounds__(256) void wgrad1x1_reduce_kernel(const float* __res
   }
 }
 
+// the fold as a launch of its own, for kernels that leave one [Ko][C] partial per workgroup themselves (csrc/conv_bnbwd.hip)
+hipError_t wgrad1x1_fold(const float* ws, float* dw, long long total4, int G, int accumulate, hipStream_t stream) {
+  hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((total4 + 15) / 16)), dim3(256), 0, stream, ws, dw, total4, G, accumulate);
+  return hipGetLastError();
+}
+
 static int g_w1_mode = -1;
 extern "C" int dle_wgrad1x1_mode(int mode) {
   const int old = g_w1_mode;
@@ -246,10 +252,7 @@ extern "C" int dle_wgrad1x1_try(const void* dy, const void* x, float* dw, int M,
 #undef W1_GO
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { dle_set_error("wgrad1x1 launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
-  const long long total4 = (long long)Ko * C / 4;
-  hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((total4 + 15) / 16)), dim3(256), 0, stream, (const float*)workspace, dw, total4,
-                     wgs, accumulate);
-  e = hipGetLastError();
+  e = wgrad1x1_fold((const float*)workspace, dw, (long long)Ko * C / 4, wgs, accumulate, stream);
   if (e != hipSuccess) { dle_set_error("wgrad1x1 reduce launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
   return 1;
 }

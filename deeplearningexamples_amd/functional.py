@@ -1109,6 +1109,67 @@ def bn_bwd_conv1x1_dgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask=N
     return dt, dx, t2 is not None
 
 
+def bn_bwd_conv1x1_dgrad_wgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, xin, gw, relu_mask=None, reduce_done=False, bnred=None):
+    """bn_bwd_conv1x1_dgrad with the convolution's weight gradient in the same kernel and WITHOUT dt: gw [K, N] (fp32, written)
+    = dt^T xin, xin [.., N] the unit's saved input.  dt is never written or read back (csrc/conv_bnbwd.hip, WG form); gw and
+    bnred's sums are accumulated in the order of wgrad1x1 / bn_bwd_conv1x1_dgrad: the same bits.  Other arguments as
+    bn_bwd_conv1x1_dgrad.
+    -> (dx [m, N], bnred taken) or None outside the kernel's envelope (nothing has been launched then).
+    (When the C side declines AFTER the reduction was launched the unfused apply + GEMM + weight gradient run here: same pair,
+    taken = False.)"""
+    C.require_cuda(dy, x, mean, rstd, gamma, dgamma, dbeta, w, xin, gw, relu_mask)
+    k = x.shape[-1]
+    m = x.numel() // k
+    n = w.shape[-1]
+    if (m < 4096 or k != 256 or n != 64 or w.numel() != k * n or xin.numel() != m * n or gw.numel() != k * n
+            or gw.dtype != torch.float32
+            or not (dy.is_contiguous() and x.is_contiguous() and w.is_contiguous() and xin.is_contiguous() and gw.is_contiguous())
+            or x.dtype not in (torch.float16, torch.bfloat16) or dy.dtype != x.dtype or w.dtype != x.dtype or xin.dtype != x.dtype
+            or os.environ.get("DLE_CONV_BNBWD", "1") == "0"
+            or any(t is not None and t.data_ptr() % 16 for t in (dy, x, w, xin, gw, relu_mask))):
+        return None
+    ws = _bn_ws(x.reshape(m, k))
+    act_bytes = 0.125 if relu_mask is not None else 0.0
+    relu_tag = "+relu" if relu_mask is not None else ""
+    if not reduce_done:
+        C.annotate(bytes=float(x.numel()) * (4 + act_bytes), tag="M%dxC%d%s" % (m, k, relu_tag))
+        C.call("dle_bn_bwd_reduce", C.ptr(dy), None, C.ptr(relu_mask), C.ptr(x), C.ptr(mean), C.ptr(rstd), C.ptr(dgamma),
+               C.ptr(dbeta), m, k, 0, C.ptr(ws), ws.numel() * 4, C.dt(x), C.stream())
+    dx = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    t2 = bits2 = mean2 = rstd2 = None
+    if bnred is not None and bnred[0].numel() == m * n and bnred[0].is_contiguous() and bnred[1] is not None \
+            and os.environ.get("DLE_RN50_FUSE_BNRED", "1") != "0" and os.environ.get("DLE_RN50_FUSE_BNRED2", "1") != "0":
+        t2, bits2, mean2, rstd2 = bnred[:4]
+    groups = int(C.lib().dle_conv1x1_bnbwd_groups(m))
+    wg_bytes = int(C.lib().dle_conv1x1_bnbwd_wgrad_workspace(m, int(t2 is not None)))
+    part_bytes = (groups * 2 * n * 4 + 15) // 16 * 16 if t2 is not None else 0
+    # ONE request for both: two requests on one stream return the same buffer, and the kernel writes both in one launch
+    buf = splitk_workspace(x.device, part_bytes + wg_bytes)
+    part = buf[:part_bytes // 4] if t2 is not None else None
+    wpart = buf[part_bytes // 4:]
+    C.annotate(bytes=float(x.numel()) * (4 + act_bytes) + (dx.numel() + xin.numel()) * 2.0
+               + dx.numel() * (2.125 if t2 is not None else 0.0),
+               flops=4.0 * m * n * k, tag="bn_bwd+dgrad+wgrad %dx%dx%d%s%s" % (m, n, k, relu_tag, "+bnred" if t2 is not None else ""))
+    rc = _timed_optional("dle_conv1x1_bnbwd_dgrad_wgrad", C.lib().dle_conv1x1_bnbwd_dgrad_wgrad,
+                         (C.ptr(dy), C.ptr(x), C.ptr(relu_mask), C.ptr(w), C.ptr(dx), C.ptr(mean), C.ptr(rstd),
+                          C.ptr(gamma), C.ptr(dgamma), C.ptr(dbeta), C.ptr(t2), C.ptr(bits2), C.ptr(mean2), C.ptr(rstd2),
+                          C.ptr(part), part_bytes, C.ptr(xin), C.ptr(gw), C.ptr(wpart), wpart.numel() * 4, m, n, k, C.dt(x),
+                          C.stream()))
+    if rc > 1:
+        C.check(rc - 1000 if rc > 1000 else -1, "dle_conv1x1_bnbwd_dgrad_wgrad")
+    if rc != 1:
+        # the C side declined with the reduction launched and dgamma / dbeta final: finish HERE, unfused
+        dt, _ = bn_bwd(dy, None, x, mean, rstd, gamma, dgamma, dbeta, relu_mask=relu_mask, reduce_done=True)
+        gemm(dt.view(m, k), w, m, n, k, True, False, out=dx)
+        if not wgrad1x1(dt.view(m, k), xin.view(m, n), gw.view(k, n)):
+            gemm(dt.view(m, k), xin.view(m, n), k, n, m, False, False, out=gw.view(k, n),
+                 splitk=pick_splitk(k, n, m, target_blocks=1024))
+        return dx, False
+    if t2 is not None:
+        C.call("dle_bn_bwd_finish", C.ptr(part), groups, n, C.ptr(bnred[4]), C.ptr(bnred[5]), 0, C.stream())
+    return dx, t2 is not None
+
+
 def maxpool_fwd(x, ksize=3, stride=2, pad=1):
     C.require_cuda(x)
     n, h, w, c = x.shape

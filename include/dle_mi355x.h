@@ -396,6 +396,19 @@ int dle_conv1x1_bnbwd_dgrad(const void* dy, const void* t, const void* relu_mask
                             const void* t2, const void* bits2, const float* mean2, const float* rstd2, float* partial,
                             int64_t partial_bytes, int M, int N, int K, int dtype, hipStream_t stream);
 int dle_conv1x1_bnbwd_groups(int M);
+/* The same launch WITH conv3's weight gradient and without dt: gw [K][N] (fp32, written) = dt^T x, x [M, N] the unit's saved input.
+ * The kernel that holds the rounded 16-bit dt in registers forms the product itself (dt and x rows through LDS, one fp32 [K][N]
+ * partial per workgroup in `workspace`, folded in workgroup order: deterministic, no atomics), so dt is never written or read
+ * back.  dx and `partial` are bit-identical to dle_conv1x1_bnbwd_dgrad, gw to dle_wgrad1x1_try on the dt that call writes (the
+ * same MFMA steps over the same tiles in the same order; bn2's per-tile values leave unsummed and a small launch adds them in
+ * the plain form's order).  workspace >= dle_conv1x1_bnbwd_wgrad_workspace(M, t2 != NULL) bytes, 16-byte aligned; with t2,
+ * partial holds dle_conv1x1_bnbwd_groups(M) rows.  1: launched; 0: outside the envelope (as above) or workspace too small. */
+int dle_conv1x1_bnbwd_dgrad_wgrad(const void* dy, const void* t, const void* relu_mask, const void* w, void* dx,
+                                  const float* mean, const float* rstd, const float* gamma, const float* dgamma,
+                                  const float* dbeta, const void* t2, const void* bits2, const float* mean2, const float* rstd2,
+                                  float* partial, int64_t partial_bytes, const void* x, float* gw, void* workspace,
+                                  int64_t workspace_bytes, int M, int N, int K, int dtype, hipStream_t stream);
+int64_t dle_conv1x1_bnbwd_wgrad_workspace(int M, int bnred);
 /* The backward reduction of a BatchNorm taken where its input gradient is PRODUCED (csrc/gemm_expand.hip, BRED): conv1's data
  * gradient of the next bottleneck, C = A B^T + src under `bits` (the DLE_ACT_ADD_MASKED form of dle_gemm), is the gradient of the
  * previous block's output; with g = C under bits2 and xhat = (t2 - mean2) rstd2 the kernel also leaves partial [groups][2][N] rows
