@@ -373,6 +373,10 @@ def gemm(a, b, m, n, k, a_kc, b_kc, out=None, out_dtype=None, bias=None, act=C.A
         raise ValueError("gemm output must have unit inner stride")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != n):
         raise ValueError("gemm bias must be fp32 [n]")
+    if mask_src is not None and m > 1 and mask_src.dim() == 2 and out.dim() == 2 and mask_src.stride(0) != out.stride(0):
+        # (the epilogues address the source tensor with the output's row pitch: another pitch would read other elements, and past
+        #  the end of a dense source behind a row-strided output)
+        raise ValueError("gemm mask_src must have the row pitch of the output (%d, got %d)" % (out.stride(0), mask_src.stride(0)))
     extra = (float(m * n) * mask_src.element_size() if mask_src is not None else 0.0) + \
             (float(aux.numel()) * aux.element_size() if aux is not None else 0.0)
     C.annotate(flops=2.0 * m * n * k,

@@ -61,7 +61,6 @@ n additions errs by at most gamma_n sum |a b| (the float64 reference of |a| and 
 import contextlib
 import ctypes
 import functools
-import math
 import zlib
 
 import pytest
@@ -69,15 +68,13 @@ import torch
 
 from deeplearningexamples_amd import _cabi as C
 from deeplearningexamples_amd import functional as F
-from tests._exact_grid import gen, grid, ulp16
+from tests._exact_grid import B_MFMA, Out as _Out, assert_same as _assert_same, gen, grid, ulp16
 
 pytestmark = pytest.mark.gpu
 
 BF, HF = torch.bfloat16, torch.float16
 DT_IDS = {BF: "bf16", HF: "fp16"}
-B_MFMA = 2.0 ** 18
 U = 2.0 ** -24
-TAIL = 4096
 F64 = torch.float64
 
 
@@ -177,36 +174,6 @@ def _summable_32(absref, *inputs, dw0=None):
     assert worst < B_MFMA, "sum of magnitudes up to %g: fp32 sums would not be exact" % worst
     if dw0 is not None:
         _on_grid(dw0)
-
-
-def _assert_same(got, want, what):
-    if torch.equal(got, want):
-        return
-    bad = got != want
-    idx = torch.nonzero(bad)[:4]
-    first = tuple(idx[0].tolist())
-    raise AssertionError("%s: %d of %d elements differ, first at %s (got %r, want %r); more at %s" % (
-        what, int(bad.sum()), bad.numel(), first, float(got[first]), float(want[first]), idx[1:].tolist()))
-
-
-def _bits(t):
-    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
-
-
-class _Out:
-    """An output as a view at the head of an over-long buffer filled with NaN (or `fill`): the tail must keep its bits."""
-
-    def __init__(self, shape, dtype, dev, fill=None):
-        self.n = math.prod(shape)
-        self.buf = torch.full((self.n + TAIL,), float("nan"), dtype=dtype, device=dev)
-        self.t = self.buf[:self.n].view(shape)
-        if fill is not None:
-            self.t.copy_(fill)
-        self.tail = _bits(self.buf[self.n:]).clone()
-
-    def check(self, what):
-        assert torch.equal(_bits(self.buf[self.n:]), self.tail), "%s wrote past the end of its output" % what
-        return self.t
 
 
 # ---------------------------------------------------------------- C ABI entry points that may decline
