@@ -180,6 +180,7 @@ _SIGS = {
                             c_float, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "dle_mt_adam_copy": (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dle_mt_ema": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_float, c_float, c_void_p]),
     "dle_wg_taps": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_i64, c_int, c_void_p]),
     "dle_wg_taps_bwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_i64, c_i64, c_int, c_void_p]),
     "dle_wg_gate_fwd": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p]),
@@ -284,7 +285,7 @@ class KernelTimer:
 
     # entry points whose duration depends on state they consume (row lists, touched-row sets): never replayed
     # (the optimizer updates are not pure either: a replay would step the weights / moments again)
-    _STATEFUL = ("emb_sgd", "emb_adam", "emb_sparse", "emb_link", "emb_grad", "amp_update", "mt_lamb", "mt_sgd", "mt_adam")
+    _STATEFUL = ("emb_sgd", "emb_adam", "emb_sparse", "emb_link", "emb_grad", "amp_update", "mt_lamb", "mt_sgd", "mt_adam", "mt_ema")
 
     def replay(self, name, tag, iters=20, warmup=3, cold=False):
         """Average duration (ms) of the recorded call re-launched back to back: ONE event pair around `iters`

@@ -6,12 +6,14 @@ Mirrors the reference's step (Classification/ConvNets/image_classification/):
     optimizers.py:34-56   SGD(momentum, nesterov, weight_decay), no weight decay for names containing "bn"
     optimizers.py:82-130  step / linear / cosine LR policies with linear warm-up (per epoch)
     utils.py:117-123      loss all-reduce across ranks (here: only when asked, never inside the step)
+    training.py:148-152,183-184 + models/common.py:191-212   exponential moving average of the model's state after every call
 Data parallelism: one process per GPU, the fp32 gradient bucket(s) are all-reduced (mean) with
 torch.distributed (backend nccl = RCCL over xGMI) on a side stream, bucket by bucket while the backward of the
 earlier layers is still running (the reference uses torch DDP's reducer, training.py:78-84).
 The step is a fixed kernel sequence (HIP-graph capturable): activations NHWC 16-bit, statistics and master
 weights fp32, gradients fp32 in ONE flat buffer whose element order matches the parameters' memory order.
 """
+import copy
 import math
 from typing import Optional
 
@@ -61,7 +63,7 @@ def lr_linear_policy(base_lr, warmup_length, epochs):
 class ResNetTrainer:
     def __init__(self, model: ResNet50, lr: float, momentum=0.875, weight_decay=3.0517578125e-05, nesterov=False,
                  label_smoothing=0.1, compute_dtype=torch.bfloat16, bn_weight_decay=False, static_loss_scale=1.0,
-                 world_size=1, process_group=None, bucket_mb=25, grad_acc_steps=1):
+                 world_size=1, process_group=None, bucket_mb=25, grad_acc_steps=1, ema=None):
         self.model = model
         # gradient accumulation (main.py:405-416 batch_size_multiplier -> training.py divide_loss / grad_acc_steps): the optimizer
         # steps every grad_acc_steps calls of train_step on the sum of the micro-batch gradients, each divided by grad_acc_steps
@@ -162,6 +164,12 @@ class ResNetTrainer:
         self.w16["fc.weight"] = self.fc_w16
         self.refresh_working_copies()
         self._build_tables()
+        # exponential moving average of the weights and BatchNorm statistics (--use-ema DECAY; training.py:148-152): None = off,
+        # nothing is allocated and the step launches what it always did
+        self.ema = None if ema is None else float(ema)
+        self.ema_model = None
+        if self.ema is not None:
+            self._build_ema()
 
     # ------------------------------------------------------------------ parameter plumbing
     @staticmethod
@@ -171,14 +179,17 @@ class ResNetTrainer:
             return p.data.permute(0, 2, 3, 1).reshape(-1)
         return p.data.reshape(-1)
 
-    def refresh_working_copies(self):
-        for u in self.units:
-            w = dict(self.model.named_parameters())[u.name_conv + ".weight"]
+    def _refresh_copies(self, model, units, stem, fc_w16):
+        for u in units:
+            w = u.conv.weight
             ko, ci, r, s = w.shape
             F.cast_rows(self._phys(w).view(ko * r * s, ci), self.dtype, cols_out=u.w16.shape[-1],
                         out=u.w16.view(ko * r * s, -1))
-        F.cast(self.model.fc.weight.data, self.dtype, out=self.fc_w16)
-        F.stem_pack_weight(self.model.conv1.weight.data, self.dtype, out=self.stem.w2)
+        F.cast(model.fc.weight.data, self.dtype, out=fc_w16)
+        F.stem_pack_weight(model.conv1.weight.data, self.dtype, out=stem.w2)
+
+    def refresh_working_copies(self):
+        self._refresh_copies(self.model, self.units, self.stem, self.fc_w16)
 
     def _stem_image(self, images):
         """Input batch -> the 16-bit NHWC image the stem reads: 4 channels (8 bytes per pixel) for its own kernels, 8 for the
@@ -214,6 +225,67 @@ class ResNetTrainer:
     def set_lr(self, lr: float):
         self.lr.fill_(lr)
 
+    # ------------------------------------------------------------------ exponential moving average (models/common.py:191-212)
+    @staticmethod
+    def _ema_entries(model):
+        """The state_dict entries the reference's EMA walks: parameters and BatchNorm running statistics, no counters."""
+        return [(k, v) for k, v in model.state_dict().items() if not k.endswith("num_batches_tracked")]
+
+    def _build_ema(self):
+        # (after the rank-0 broadcast in the constructor: every replica's average starts from the same weights)
+        self.ema_model = copy.deepcopy(self.model)
+        xs, es = [], []
+        for (k, x), (ke, e) in zip(self._ema_entries(self.model), self._ema_entries(self.ema_model)):
+            # one flat pass is element-for-element right only if both tensors are dense in the SAME memory order
+            assert k == ke and x.shape == e.shape and x.stride() == e.stride(), "EMA copy of %s lost the master's layout" % k
+            assert x.dtype == torch.float32 and e.dtype == torch.float32, "EMA runs on the fp32 master state (%s)" % k
+            px, pe = self._phys(x), self._phys(e)
+            assert px.data_ptr() == x.data_ptr() and pe.data_ptr() == e.data_ptr(), "%s is not dense in memory order" % k
+            xs.append(px)
+            es.append(pe)
+        self.t_ema = mt.TensorTable([xs, es], chunk=mt.streaming_chunk([xs]))
+        # {mu_t, 1 - mu_t} on the device: a captured step reads them, set_ema_step() rewrites them between replays
+        self.ema_coef = torch.empty(2, dtype=torch.float32, device=self.dev)
+        self._ema_coef_views = (self.ema_coef[0:1], self.ema_coef[1:2])
+        self._ema_mu_t = None
+        self.set_ema_step(None)
+        # evaluation units over the averaged model with their own 16-bit working copies, refreshed lazily: an update only
+        # marks them stale, the first averaged inference after it re-casts them
+        self.ema_stem, self.ema_blocks = self.ema_model.units()
+        self.ema_units = [self.ema_stem] + [u for blk in self.ema_blocks for u in blk if u is not None]
+        for u, src in zip(self.ema_units, self.units):
+            u.w16 = torch.zeros_like(src.w16)
+        self.ema_stem.w2 = torch.zeros_like(self.stem.w2)
+        self.ema_fc_w16 = torch.empty_like(self.fc_w16)
+        self.ema_dirty = True
+
+    def set_ema_step(self, step):
+        """The decay of the NEXT update(s): mu_t = mu if step is None else min(mu, (1 + step) / (10 + step)) in Python doubles,
+        1 - mu_t in double too, both rounded to fp32 once (what the reference's tensor ops do with their Python scalars).
+        Written to the device without a host sync, like set_lr; unchanged values (the ramp ends after ~10 / (1 - mu) steps)
+        are not written again.  Also marks the averaged model's 16-bit copies stale, so call it before every replay of a
+        captured step."""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no averaged model: construct it with ema=<decay>")
+        mu_t = self.ema if step is None else min(self.ema, (1.0 + step) / (10 + step))
+        if mu_t != self._ema_mu_t:
+            self._ema_coef_views[0].fill_(mu_t)
+            self._ema_coef_views[1].fill_(1.0 - mu_t)
+            self._ema_mu_t = mu_t
+        self.ema_dirty = True       # (the replay of a captured step runs no Python: this call is what announces its update)
+
+    def mark_ema_dirty(self):
+        """The averaged model changed behind the trainer's back (a checkpoint load): its 16-bit copies are stale."""
+        self.ema_dirty = True
+
+    def _ema_eval_state(self):
+        if self.ema is None:
+            raise ValueError("this trainer keeps no averaged model: construct it with ema=<decay>")
+        if self.ema_dirty:
+            self._refresh_copies(self.ema_model, self.ema_units, self.ema_stem, self.ema_fc_w16)
+            self.ema_dirty = False
+        return self.ema_model, self.ema_stem, self.ema_blocks, self.ema_fc_w16
+
     # ------------------------------------------------------------------ communication
     def set_side_streams(self, enabled):
         """Second / third stream on or off (off: every kernel in line on the current stream -- bench.py's per-kernel timing pass)."""
@@ -235,21 +307,23 @@ class ResNetTrainer:
             images = images.contiguous()         # --memory-format nhwc loaders hand over channels_last tensors
         return images
 
-    def infer(self, images):
+    def infer(self, images, ema=False):
         """Evaluation-mode forward (Executor.forward under model.eval(), training.py:98-105): running BatchNorm statistics,
-        no state kept.  -> fp32 logits [N, classes]."""
+        no state kept.  -> fp32 logits [N, classes].  ema=True: the same forward over the averaged model (the reference's
+        `val_ema` step, training.py:188-192)."""
+        model, stem, blocks, fc_w16 = self._ema_eval_state() if ema else (self.model, self.stem, self.blocks, self.fc_w16)
         x = self._stem_image(self._input(images))
-        h, _ = F.maxpool_fwd(self.stem.forward_eval(x))
-        for (u1, u2, u3, ud) in self.blocks:
+        h, _ = F.maxpool_fwd(stem.forward_eval(x))
+        for (u1, u2, u3, ud) in blocks:
             res = ud.forward_eval(h) if ud is not None else h
             h = u3.forward_eval(u2.forward_eval(u1.forward_eval(h)), residual=res)
         pooled = F.avgpool_fwd(h)
-        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
-                      out_dtype=torch.float32, bias=self.model.fc.bias.data)
+        return F.gemm(pooled, fc_w16, pooled.shape[0], fc_w16.shape[0], fc_w16.shape[1], True, True,
+                      out_dtype=torch.float32, bias=model.fc.bias.data)
 
-    def eval_step(self, images, target):
+    def eval_step(self, images, target, ema=False):
         """-> (loss [1] (plain cross entropy, as NLLMultiLabelSmooth / LabelSmoothing / CrossEntropyLoss evaluate), logits)."""
-        logits = self.infer(images)
+        logits = self.infer(images, ema=ema)
         loss, _ = F.softmax_xent(logits, target, smoothing=0.0)
         return loss, logits
 
@@ -386,10 +460,25 @@ class ResNetTrainer:
         F.cast_rows(self._phys(w).view(ko * r * s, ci), self.dtype, cols_out=u.w16.shape[-1], out=u.w16.view(ko * r * s, -1))
         self.first_step = False
 
-    def train_step(self, images, target):
+    def train_step(self, images, target, step=None):
         """One call of the reference's Trainer.train_step (training.py:167-186): forward + backward of one (micro-)batch and,
         every grad_acc_steps calls, the optimizer step.  Returns the device-resident fp32 loss [1] (no host sync), divided by
-        grad_acc_steps like the reference's `loss /= divide_loss`."""
+        grad_acc_steps like the reference's `loss /= divide_loss`.
+        With ema=<decay> the averaged model moves after EVERY call -- micro-batches that do not step the optimizer and steps the
+        loss scaler skips included (training.py:183-184) -- as the last launch of the call, on the current stream: behind the
+        optimizer and behind the forward's running-statistics updates, whose side streams the backward pass has joined by then.
+        step (epoch * len(loader) + i, training.py:226,373) picks the warm-up decay through set_ema_step(); without it the
+        coefficients on the device stay as they are.  A captured step (utils/graph.py) is recorded WITHOUT step: the caller
+        calls set_ema_step(k) before each replay."""
+        loss = self._train_step(images, target)
+        if self.ema is not None:
+            if step is not None:
+                self.set_ema_step(step)
+            mt.ema(self.t_ema, self.ema, coef=self.ema_coef)
+            self.ema_dirty = True
+        return loss
+
+    def _train_step(self, images, target):
         sc = self.scaler
         acc = self.grad_acc_steps
         self.steps_since_update += 1

@@ -3,10 +3,11 @@
 Mirrors Classification/ConvNets/main.py:89-356 (flags), :359-608 (prepare_for_training: resume, loss choice, loaders, optimizer,
 LR policy), :611-650 (main) and image_classification/training.py:205-254 (train), :257-311 (validate), :314-432 (train_loop:
 per-epoch validation, best_prec1, checkpoint_{epoch:04}.pth.tar through utils.Checkpointer, early stopping), logger.py's metric
-names (train.loss, train.compute_ips, train.total_ips, train.lr, val.top1, val.top5, val.loss).  Launch one process per GPU:
+names (train.loss, train.compute_ips, train.total_ips, train.lr, val.top1, val.top5, val.loss, and val_ema.* under --use-ema).
+Launch one process per GPU:
     python -m torch.distributed.run --nproc-per-node 8 -m deeplearningexamples_amd.convnets.main \
         --arch resnet50 --data-backend synthetic --batch-size 256 --amp --epochs 1 --prof 100 /data/imagenet
-Flags of the reference that select machinery outside this path (DALI, TorchScript, EMA, RMSprop, other architectures) are
+Flags of the reference that select machinery outside this path (DALI, TorchScript, RMSprop, other architectures) are
 parsed and rejected with a message instead of an argparse error.
 """
 import argparse
@@ -70,7 +71,8 @@ def add_parser_arguments(parser):
     p.add_argument("--workspace", default="./")
     p.add_argument("--memory-format", default="nchw", choices=["nchw", "nhwc"],
                    help="layout of the LOADER's batches; the kernels compute in NHWC either way")
-    p.add_argument("--use-ema", default=None, type=float)
+    p.add_argument("--use-ema", default=None, type=float, metavar="DECAY",
+                   help="keep an exponential moving average of the weights and BatchNorm statistics, validate it as val_ema")
     p.add_argument("--augmentation", default=None, choices=[None, "autoaugment"])
     p.add_argument("--gpu-affinity", default="none")
     p.add_argument("--topk", default=5, type=int)
@@ -89,8 +91,6 @@ def _reject_unbuilt(args):
         raise SystemExit("--data-backend %s: DALI is not part of this path; use pytorch or synthetic" % args.data_backend)
     if args.optimizer != "sgd":
         raise SystemExit("--optimizer rmsprop (the EfficientNet recipe) is not built; ResNet-50 trains with sgd")
-    if args.use_ema is not None:
-        raise SystemExit("--use-ema (the EfficientNet recipe) is not built")
     if args.augmentation is not None:
         raise SystemExit("--augmentation autoaugment needs PIL image ops on the host: not built")
     if not args.amp:
@@ -114,13 +114,14 @@ def accuracy(output, target, topk=(1,)):
     return [correct[:k].float().sum() * (100.0 / target.size(0)) for k in topk]
 
 
-def train(trainer, loader, lr_fn, args, epoch, world):
-    """training.py:205-254."""
+def train(trainer, loader, lr_fn, args, epoch, world, step=0):
+    """training.py:205-254.  step: the global iteration the epoch starts at (epoch * len(loader), training.py:373), which
+    picks the warm-up decay of the weight average."""
     n, t_prev = 0, time.time()
     for i, (x, y) in enumerate(loader):
         lr = float(lr_fn(i))
         trainer.set_lr(lr)
-        loss = trainer.train_step(x, y)
+        loss = trainer.train_step(x, y, step=step + i)
         n += 1
         if i % args.print_freq == 0:
             loss_v = float(trainer.reduced_loss(loss).item())           # utils.reduce_tensor; the only host sync of the loop
@@ -135,11 +136,13 @@ def train(trainer, loader, lr_fn, args, epoch, world):
     return n
 
 
-def validate(trainer, loader, args, epoch, world):
-    """training.py:257-311: evaluation-mode forward, loss + top-1 / top-k, averaged over the batches (and ranks)."""
+def validate(trainer, loader, args, epoch, world, eval_step=None, prefix="val"):
+    """training.py:257-311: evaluation-mode forward, loss + top-1 / top-k, averaged over the batches (and ranks).
+    eval_step / prefix: the inference function and metric prefix of one entry of Trainer.validation_steps (training.py:188-192)."""
+    eval_step = eval_step or trainer.eval_step
     s1 = sk = sl = cnt = 0.0
     for i, (x, y) in enumerate(loader):
-        loss, out = trainer.eval_step(x, y)
+        loss, out = eval_step(x, y)
         p1, pk = accuracy(out, y, (1, args.topk))
         vals = torch.stack([p1, pk, loss.reshape(())])
         if world > 1:
@@ -151,10 +154,10 @@ def validate(trainer, loader, args, epoch, world):
         if 0 < args.prof <= i + 1:
             break
     cnt = max(cnt, 1.0)
-    res = {"val.top1": s1 / cnt, "val.top%d" % args.topk: sk / cnt, "val.loss": sl / cnt}
+    res = {prefix + ".top1": s1 / cnt, prefix + ".top%d" % args.topk: sk / cnt, prefix + ".loss": sl / cnt}
     if is_main_process():
         dllogger.log(step=(epoch,), data=res)
-    return res["val.top1"]
+    return res[prefix + ".top1"]
 
 
 def train_loop(trainer, args, lr_policy, train_loader, train_len, val_loader, start_epoch, best_prec1, world):
@@ -166,10 +169,15 @@ def train_loop(trainer, args, lr_policy, train_loader, train_len, val_loader, st
     print("RUNNING EPOCHS FROM %d TO %d" % (start_epoch, end_epoch))
     for epoch in range(start_epoch, end_epoch):
         if not args.evaluate:
-            iters += train(trainer, train_loader, lambda i: lr_policy(i, epoch), args, epoch, world)
+            iters += train(trainer, train_loader, lambda i: lr_policy(i, epoch), args, epoch, world, step=epoch * train_len)
         prec1 = -1
         if not args.training_only:
             prec1 = validate(trainer, val_loader, args, epoch, world)
+            if trainer.ema is not None:
+                # the averaged model is validated and logged beside the model; best_prec1, is_best and early stopping follow
+                # the plain `val` result only (training.py:376-401)
+                validate(trainer, val_loader, args, epoch, world, eval_step=lambda x, y: trainer.eval_step(x, y, ema=True),
+                         prefix="val_ema")
             is_best = prec1 > best_prec1
             best_prec1 = max(prec1, best_prec1)
         else:
@@ -217,7 +225,7 @@ def main(argv=None):
     trainer = ResNetTrainer(model, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
                             nesterov=args.nesterov, label_smoothing=args.label_smoothing, compute_dtype=dtype,
                             static_loss_scale=args.static_loss_scale, world_size=world,
-                            bn_weight_decay=args.bn_weight_decay, grad_acc_steps=bsm)
+                            bn_weight_decay=args.bn_weight_decay, grad_acc_steps=bsm, ema=args.use_ema)
     start_epoch, best_prec1 = 0, 0.0
     if args.resume is not None:                  # main.py:419-452
         if os.path.isfile(args.resume):

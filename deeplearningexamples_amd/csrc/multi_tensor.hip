@@ -534,6 +534,48 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_adam_copy(const long long* __rest
   }
 }
 
+// -------------------------------------------------------------------- exponential moving average of a model's state
+// CN/image_classification/models/common.py:191-212 (EMA.__call__): ema.mul_(mu); ema.add_((1 - mu) * x) on every state_dict entry.
+// lists: 0 = x (the source parameter / buffer, fp32, read only), 1 = e (the shadow, fp32, updated in place).
+// Three fp32 roundings per element and NO fused multiply-add, exactly as the two tensor ops leave them:
+//   e' = rn( rn(mu * e) + rn(omm * x) ),  omm = fp32(1.0 - mu) taken in double by the caller.
+// Contraction is switched off for the function: a v_fma of the first product into the sum changes about a quarter of the
+// elements at mu = 0.9999.  coef_ptr (nullable): {mu, 1 - mu} on the device, so a captured step carries no by-value scalar that
+// changes from step to step (the lr_ptr / lr_host convention).  No skip flag: the average moves on skipped steps too.
+__device__ __forceinline__ float mt_ema1(float e, float x, float mu, float omm) {
+#pragma clang fp contract(off)
+  const float a = mu * e;
+  const float b = omm * x;
+  return a + b;
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void mt_ema(const long long* __restrict__ table, int n, int chunk,
+                                                   const float* __restrict__ coef_ptr, float mu_host, float omm_host) {
+  const MtTable t = mt_view(table, n);
+  const long long c = blockIdx.x;
+  const int ti = mt_find(t, c);
+  const long long off = (c - t.chunk_start[ti]) * chunk;
+  long long len = t.size[ti] - off;
+  if (len > chunk) len = chunk;
+  const float mu = coef_ptr ? coef_ptr[0] : mu_host;
+  const float omm = coef_ptr ? coef_ptr[1] : omm_host;
+  const float* x = (const float*)t.ptr[0 * n + ti] + off;
+  float* e = (float*)t.ptr[1 * n + ti] + off;
+  const bool vec = ((((uintptr_t)x) | ((uintptr_t)e)) & 15) == 0;
+  const long long len4 = len & ~3LL;
+  for (long long i = (long long)threadIdx.x * 4; i < len; i += MT_BLOCK * 4) {
+    if (i < len4) {
+      const float4_t rx = ld4<DLE_F32>(x + i, vec);
+      float4_t re = ld4<DLE_F32>(e + i, vec);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) re[k] = mt_ema1(re[k], rx[k], mu, omm);
+      st4<DLE_F32>(e + i, re, vec);
+    } else {
+      for (long long k = i; k < len; ++k) e[k] = mt_ema1(e[k], x[k], mu, omm);
+    }
+  }
+}
+
 // param_norm[t] / update_norm[t] = sqrt of tensor t's chunk partials (the fold of mt_l2norm_finish, both arrays in one launch)
 __global__ __launch_bounds__(MT_BLOCK) void mt_lamb_norms_finish(const float* __restrict__ partial_p, const float* __restrict__ partial_u,
                                                                  const long long* __restrict__ table, int n,
@@ -714,6 +756,17 @@ extern "C" int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t
   else if (copy_dtype == DLE_BF16) GO(DLE_BF16);
   else GO(-1);
 #undef GO
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dle_mt_ema(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, const float* coef_dev,
+                          float mu_host, float one_minus_mu_host, hipStream_t stream) {
+  DLE_CHECK_ARG(table_dev, "mt_ema: null table");
+  DLE_CHECK_ARG(chunk > 0 && chunk % 4 == 0, "mt_ema: chunk must be a positive multiple of 4");
+  if (n_tensors == 0 || total_chunks == 0) return 0;
+  hipLaunchKernelGGL(mt_ema, dim3((unsigned)total_chunks), dim3(MT_BLOCK), 0, stream, (const long long*)table_dev, n_tensors,
+                     chunk, coef_dev, mu_host, one_minus_mu_host);
   DLE_LAUNCH_CHECK();
   return 0;
 }

@@ -177,3 +177,19 @@ def adam_copy(table, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, skip_flag=None,
     C.call("dle_mt_adam_copy", C.ptr(table.table), table.n, table.total_chunks, table.chunk, copy_dt, C.ptr(skip_flag), C.ptr(lr_dev),
            0.0 if lr_dev is not None else float(lr), beta1, beta2, eps, C.ptr(step), C.ptr(inv_scale), C.ptr(tensor_mul),
            C.stream())
+
+
+def ema(table, mu, one_minus_mu=None, coef=None):
+    """lists: x (source), e (shadow), both fp32: e = e * mu + (1 - mu) * x with the three fp32 roundings of the reference's
+    `ema.mul_(mu); ema.add_((1 - mu) * x)` (CN/image_classification/models/common.py:191-212) -- bit-identical to those two ops.
+    mu is a Python double; one_minus_mu defaults to 1.0 - mu taken in double, as the reference takes it before the tensor op casts.
+    coef: fp32 device tensor {mu, 1 - mu} read by the kernel instead of the host values (a captured step replays with whatever it
+    holds).  x is not written; there is no skip flag."""
+    if table.n_lists != 2 or any(d != torch.float32 for d in table.dtypes):
+        raise ValueError("ema expects two fp32 lists: the source tensors and their averages")
+    if coef is not None and (coef.dtype != torch.float32 or coef.numel() != 2 or coef.device != table.device):
+        raise ValueError("coef: fp32 [2] = {mu, 1 - mu} on the table's device")
+    mu = float(mu)
+    omm = 1.0 - mu if one_minus_mu is None else float(one_minus_mu)
+    _note(table, 12)                     # reads x and e, writes e
+    C.call("dle_mt_ema", C.ptr(table.table), table.n, table.total_chunks, table.chunk, C.ptr(coef), mu, omm, C.stream())

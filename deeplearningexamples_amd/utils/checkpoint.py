@@ -4,7 +4,8 @@ into the reference's own classes and the other way round.
 Formats (paths relative to /root/reference/PyTorch/):
  * ResNet-50    Classification/ConvNets/image_classification/training.py:194-202,409-421, utils.py:26-80
      checkpoint_{epoch:04}.pth.tar (+ copies checkpoint.pth.tar / model_best.pth.tar) = torch.save of
-     {"epoch", "best_prec1", "state_dict": model.state_dict(), "optimizer": torch.optim.SGD.state_dict()} with the
+     {"epoch", "best_prec1", "state_dict": model.state_dict(), "optimizer": torch.optim.SGD.state_dict()
+      [, "state_dict_ema": the averaged model's state_dict() under --use-ema]} with the
      parameter groups of get_sgd_optimizer (optimizers.py:34-56): [names containing "bn": weight_decay 0 | the rest].
  * BERT         LanguageModeling/BERT/run_pretraining.py:489-515, lamb_amp_opt/fused_lamb/fused_lamb.py:13-41,131-260
      ckpt_{step}.pt = {"model": state_dict, "optimizer": FusedLAMBAMP.state_dict(), "grad_scaler": GradScaler
@@ -124,9 +125,13 @@ def rn50_trainer_state(trainer, epoch, best_prec1=0.0, lr=None):
                 mom[n] = m.view(ko, r, s, ci).permute(0, 3, 1, 2).clone(memory_format=torch.preserve_format)
             else:
                 mom[n] = m.view(p.shape).clone()
-    return {"epoch": epoch, "best_prec1": best_prec1, "state_dict": model.state_dict(),
-            "optimizer": rn50_optimizer_state(named, mom, float(trainer.lr.item()) if lr is None else lr, trainer.momentum,
-                                              trainer.wd, trainer.nesterov, trainer.bn_weight_decay)}
+    state = {"epoch": epoch, "best_prec1": best_prec1, "state_dict": model.state_dict(),
+             "optimizer": rn50_optimizer_state(named, mom, float(trainer.lr.item()) if lr is None else lr, trainer.momentum,
+                                               trainer.wd, trainer.nesterov, trainer.bn_weight_decay)}
+    if getattr(trainer, "ema_model", None) is not None:
+        # training.py:194-202: the averaged model under the model's own keys (its num_batches_tracked are never advanced)
+        state["state_dict_ema"] = trainer.ema_model.state_dict()
+    return state
 
 
 def rn50_trainer_load(trainer, checkpoint):
@@ -145,6 +150,12 @@ def rn50_trainer_load(trainer, checkpoint):
     trainer.first_step = not mom
     trainer.steps_done = int(model.bn1.num_batches_tracked.item())
     trainer.refresh_working_copies()
+    if getattr(trainer, "ema_model", None) is not None:
+        # main.py:431-432,593-597: the reference builds its trainer (deepcopy) AFTER the model state is loaded, then loads
+        # state_dict_ema over the copy when the file has one.  A trainer without EMA ignores the key, as the reference does.
+        ema_sd = checkpoint.get("state_dict_ema")
+        trainer.ema_model.load_state_dict(_strip_module(ema_sd) if ema_sd is not None else model.state_dict())
+        trainer.mark_ema_dirty()
     return checkpoint.get("epoch", 0), checkpoint.get("best_prec1", 0.0)
 
 

@@ -598,6 +598,15 @@ int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t total_chun
                      const float* skip_flag_dev, const float* lr_dev, float lr_host, float beta1, float beta2, float eps,
                      const int* step_dev, const float* inv_scale_dev, const float* tensor_mul_dev, hipStream_t stream);
 
+/* ---- exponential moving average of a model's state over a tensor table (csrc/multi_tensor.hip): EMA.__call__ of
+ * Classification/ConvNets/image_classification/models/common.py:191-212, `ema.mul_(mu); ema.add_((1 - mu) * x)` on every
+ * state_dict entry, run after each Trainer.train_step (training.py:148-152,183-184).  lists: x (source, fp32, read only),
+ * e (shadow, fp32, in place).  e' = rn(rn(mu * e) + rn(one_minus_mu * x)): the three fp32 roundings of the two tensor ops, no
+ * fused multiply-add -- bit-identical to them.  coef_dev: two fp32 device words {mu, 1 - mu} (the caller takes 1 - mu in double), or
+ * NULL: the two host values are used.  No skip flag: the average also moves on steps the loss scaler skips. */
+int dle_mt_ema(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, const float* coef_dev, float mu_host,
+               float one_minus_mu_host, hipStream_t stream);
+
 /* ---- WaveGlow training step (csrc/waveglow.hip): SpeechSynthesis/Tacotron2/waveglow/model.py + loss_function.py -------
  * Channels-last: a series [B, C, T] of the reference is the matrix [B*T, C]; Conv1d = dle_gemm over rows.  The flow state
  * is fp32 [M, 8] (M = B*T/8 groups of n_group = 8 samples); a flow with c remaining channels works on columns [8-c, 8).
