@@ -201,6 +201,8 @@ _SIGS = {
     "dle_wg_weight_norm_fwd_batched": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p]),
     "dle_wg_weight_norm_bwd_batched": (c_int, [c_void_p, c_int, c_i64, c_void_p]),
     "dle_wg_logdet_inv_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dle_wg_flow_inv": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "dle_wg_flow_inv_first": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_int, c_void_p]),
     "dle_t2_tanh_fwd": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "dle_t2_lstm_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
                                 c_i64, c_float, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),

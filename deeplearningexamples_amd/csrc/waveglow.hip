@@ -556,6 +556,97 @@ __global__ __launch_bounds__(WG_BLOCK) void wg_upsample_weight_bwd_kernel(const 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Inference (WaveGlow.infer, model.py:251-267): one flow of the reverse pass on the fp32 state, one thread per row.
+//   audio_1 = (audio_1 - b) * exp(-log_s)      (b | log_s | 0) = o, the layout wg_coupling_fwd reads
+//   active channels [off, 8) <- W^-1 (audio_0 | audio_1)      WinvT as wg_logdet_inv writes it, embedded as diag(I_off, W^-1)
+//   early > 0: channels [off - early, off) <- sigma * noise[:, z_col .. z_col + early)   (noise: fp32 [M, 8] rows)
+//   a0 (16-bit [M, 8], optional): the first next_c / 2 channels from 8 - next_c of the NEW state, zero padded -- the `start`
+//   operand of the flow that runs next (k - 1), the shape wg_invconv_fwd emits.
+// Channels below off - early pass through bit for bit.  out may be the state itself (a row is read whole before it is written).
+__device__ __forceinline__ void wg_embed_winv8(const float* __restrict__ WinvT, float* w8, int c) {
+  const int off = 8 - c;
+  if (threadIdx.x < 64) {
+    const int j = threadIdx.x >> 3, i = threadIdx.x & 7;
+    float v = (i == j) ? 1.0f : 0.0f;
+    if (j >= off && i >= off) v = WinvT[(i - off) * c + (j - off)];       // W^-1[j, i] = WinvT[i, j]
+    w8[threadIdx.x] = v;
+  }
+  __syncthreads();
+}
+
+template <int DT>
+__device__ __forceinline__ void wg_store_a0(unsigned short* __restrict__ a0, long long m, const float* v, int next_c) {
+  const int noff = 8 - next_c, nnh = next_c >> 1;
+  float h[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float t = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (e < nnh && q == noff + e) t = v[q];
+    h[e] = t;
+  }
+  *(ushort8_t*)(a0 + m * 8) = pack8<DT>(h);
+}
+
+template <int DT>
+__global__ __launch_bounds__(WG_BLOCK) void wg_flow_inv_kernel(const float* state, const float* __restrict__ o,
+                                                               const float* __restrict__ WinvT,
+                                                               const float* __restrict__ noise, float* out,
+                                                               unsigned short* __restrict__ a0, long long M, int c, int early,
+                                                               int z_col, float sigma, int next_c) {
+  __shared__ float w8[64];
+  wg_embed_winv8(WinvT, w8, c);
+  const int off = 8 - c, nh = c >> 1;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+    float xi[8], oi[8], yo[8];
+    wg_ld8(state + m * 8, xi);
+    wg_ld8(o + m * 8, oi);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) if (i < nh && q == off + nh + i) xi[q] = (xi[q] - oi[i]) * expf(-oi[nh + i]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float acc = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc += w8[j * 8 + i] * xi[i];
+      yo[j] = j < off ? xi[j] : acc;
+    }
+    if (early > 0) {
+      float zi[8];
+      wg_ld8(noise + m * 8, zi);
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int s = 0; s < 8; ++s) if (q >= off - early && q < off && s == z_col + q - (off - early)) yo[q] = sigma * zi[s];
+    }
+    wg_st8(out + m * 8, yo);
+    if (a0) wg_store_a0<DT>(a0, m, yo, next_c);
+  }
+}
+
+// The starting state (model.py:245-249): channels [8 - c, 8) = sigma * noise[:, 0 .. c), the others 0, + the first a0.
+template <int DT>
+__global__ __launch_bounds__(WG_BLOCK) void wg_flow_inv_first_kernel(const float* __restrict__ noise, float* __restrict__ out,
+                                                                     unsigned short* __restrict__ a0, long long M, int c,
+                                                                     float sigma) {
+  const int off = 8 - c;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+    float zi[8], yo[8];
+    wg_ld8(noise + m * 8, zi);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      float t = 0.f;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) if (q >= off && s == q - off) t = sigma * zi[s];
+      yo[q] = t;
+    }
+    wg_st8(out + m * 8, yo);
+    if (a0) wg_store_a0<DT>(a0, m, yo, c);
+  }
+}
+
 // =============================================================================================== C ABI
 #define WG_DT_CHECK(what) DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, what ": 16-bit dtypes only (got %d)", dtype)
 #define WG_AL16(p) ((((uintptr_t)(p)) & 15) == 0)
@@ -802,6 +893,45 @@ extern "C" int dle_wg_logdet_inv_batched(const float* base, const int64_t* table
   DLE_CHECK_ARG(base && table_dev && logdets && WinvT && n_flows > 0, "wg_logdet_inv_batched: bad args");
   hipLaunchKernelGGL(wg_logdet_inv_batched_kernel, dim3(n_flows), dim3(64), 0, stream, base, (const long long*)table_dev,
                      logdets, WinvT, signs);
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+// noise: fp32 [M, 8] rows (row m = the 8 channels of the reference's z[b, :, t]); next_c = 0 / a0_16 = NULL: no operand is written
+extern "C" int dle_wg_flow_inv(const float* state, const float* o, const float* WinvT, const float* noise, float* out,
+                               void* a0_16, int64_t M, int c, int early, int z_col, float sigma, int next_c, int dtype,
+                               hipStream_t stream) {
+  DLE_CHECK_ARG(state && o && WinvT && out && M > 0, "wg_flow_inv: bad args");
+  WG_C_CHECK("wg_flow_inv");
+  DLE_CHECK_ARG(early >= 0 && (early & 1) == 0 && early <= 8 - c, "wg_flow_inv: 0 <= early <= 8 - c, early even (got %d)", early);
+  DLE_CHECK_ARG(early == 0 || (noise && z_col >= 0 && z_col + early <= 8), "wg_flow_inv: early > 0 needs noise and 0 <= z_col <= 8 - early");
+  DLE_CHECK_ARG(!a0_16 || (next_c >= c + early && next_c <= 8 && (next_c & 1) == 0),
+                "wg_flow_inv: c + early <= next_c <= 8, next_c even (got %d)", next_c);
+  DLE_CHECK_ARG(WG_AL16(state) && WG_AL16(o) && WG_AL16(noise) && WG_AL16(out) && WG_AL16(a0_16),
+                "wg_flow_inv: 16-byte aligned tensors");
+  if (a0_16) WG_DT_CHECK("wg_flow_inv");
+  if (dtype == DLE_BF16)
+    hipLaunchKernelGGL(wg_flow_inv_kernel<DLE_BF16>, dim3(wg_grid(M)), dim3(WG_BLOCK), 0, stream, state, o, WinvT, noise, out,
+                       (unsigned short*)a0_16, (long long)M, c, early, z_col, sigma, next_c);
+  else
+    hipLaunchKernelGGL(wg_flow_inv_kernel<DLE_F16>, dim3(wg_grid(M)), dim3(WG_BLOCK), 0, stream, state, o, WinvT, noise, out,
+                       (unsigned short*)a0_16, (long long)M, c, early, z_col, sigma, next_c);
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dle_wg_flow_inv_first(const float* noise, float* out, void* a0_16, int64_t M, int c, float sigma, int dtype,
+                                     hipStream_t stream) {
+  DLE_CHECK_ARG(noise && out && M > 0, "wg_flow_inv_first: bad args");
+  WG_C_CHECK("wg_flow_inv_first");
+  DLE_CHECK_ARG(WG_AL16(noise) && WG_AL16(out) && WG_AL16(a0_16), "wg_flow_inv_first: 16-byte aligned tensors");
+  if (a0_16) WG_DT_CHECK("wg_flow_inv_first");
+  if (dtype == DLE_BF16)
+    hipLaunchKernelGGL(wg_flow_inv_first_kernel<DLE_BF16>, dim3(wg_grid(M)), dim3(WG_BLOCK), 0, stream, noise, out,
+                       (unsigned short*)a0_16, (long long)M, c, sigma);
+  else
+    hipLaunchKernelGGL(wg_flow_inv_first_kernel<DLE_F16>, dim3(wg_grid(M)), dim3(WG_BLOCK), 0, stream, noise, out,
+                       (unsigned short*)a0_16, (long long)M, c, sigma);
   DLE_LAUNCH_CHECK();
   return 0;
 }

@@ -1,1 +1,2 @@
-"""WaveGlow training step (SpeechSynthesis/Tacotron2, `-m WaveGlow`) on the gfx950 library: SURVEY.md 8 row f1."""
+"""WaveGlow (SpeechSynthesis/Tacotron2, `-m WaveGlow`) on the gfx950 library: the training step and mel-to-audio inference
+(SURVEY.md 8 row f1)."""

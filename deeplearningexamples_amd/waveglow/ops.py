@@ -234,3 +234,50 @@ def logdet_inv_batched(flat, tab, logdets, winv_t_all, signs):
     C.require_cuda(flat, logdets, winv_t_all, signs)
     C.call("dle_wg_logdet_inv_batched", C.ptr(flat), C.ptr(tab.table), C.ptr(logdets), C.ptr(winv_t_all), C.ptr(signs), tab.n,
            C.stream())
+
+
+# ---------------------------------------------------------------- inference (WaveGlow.infer, model.py:234-272)
+def mel_rows(mel, out):
+    """fp32 mel [B, Cm, frames] -> out: 16-bit rows [B*frames, Cm] (channels last), the upsampling GEMM's input."""
+    C.require_cuda(mel, out)
+    b, cm, frames = mel.shape
+    if mel.dtype != torch.float32 or not mel.is_contiguous() or not out.is_contiguous() or out.shape != (b * frames, cm):
+        raise ValueError("mel_rows: contiguous fp32 [B, Cm, frames] -> contiguous [B*frames, Cm]")
+    C.call("dle_nchw_to_nhwc", C.ptr(mel), C.ptr(out), b, cm, frames, cm, C.dt(out), C.stream())
+    return out
+
+
+def flow_inv_first(noise, c, sigma, out, a0):
+    """The starting state: out[:, 8-c:] = sigma * noise[:, :c], the other columns 0; a0 = its first c/2 active columns, 16-bit."""
+    C.require_cuda(noise, out, a0)
+    m = _state(noise, "flow_inv_first noise")
+    _state(out, "flow_inv_first out")
+    if a0 is not None and (a0.shape != (m, 8) or not a0.is_contiguous()):
+        raise ValueError("flow_inv_first: a0 must be a contiguous 16-bit [M, 8] matrix")
+    C.call("dle_wg_flow_inv_first", C.ptr(noise), C.ptr(out), C.ptr(a0), m, c, float(sigma), C.dt(a0) if a0 is not None else C.F16,
+           C.stream())
+    return out, a0
+
+
+def flow_inv(state, o, winv_t, c, out=None, a0=None, next_c=0, early=0, noise=None, z_col=0, sigma=1.0):
+    """One flow of the reverse pass: the upper active half <- (audio_1 - b) * exp(-log_s), (b | log_s) = o[:, :c]; W^-1 on columns
+    [8-c, 8); early > 0: columns [8-c-early, 8-c) <- sigma * noise[:, z_col:z_col+early]; a0 (16-bit [M, 8], optional) <- the
+    `start` operand of the next flow to run, which has next_c remaining channels.  out may be state.  -> (out, a0)."""
+    C.require_cuda(state, o, winv_t, out, a0, noise)
+    m = _state(state, "flow_inv")
+    _state(o, "flow_inv o")
+    if out is None:
+        out = torch.empty_like(state)
+    _state(out, "flow_inv out")
+    if noise is not None:
+        _state(noise, "flow_inv noise")
+    if out.shape[0] != m or o.shape[0] != m or (noise is not None and noise.shape[0] != m):
+        raise ValueError("flow_inv: state, o, out and noise must have the same number of rows")
+    if winv_t.dtype != torch.float32 or winv_t.numel() < c * c or not winv_t.is_contiguous():
+        raise ValueError("flow_inv: winv_t must hold c*c contiguous fp32 values")
+    if a0 is not None and (a0.shape != (m, 8) or not a0.is_contiguous()):
+        raise ValueError("flow_inv: a0 must be a contiguous 16-bit [M, 8] matrix")
+    C.annotate(bytes=float(m) * 8 * (12 + (4 if early else 0) + (2 if a0 is not None else 0)), tag="%dx8 c%d" % (m, c))
+    C.call("dle_wg_flow_inv", C.ptr(state), C.ptr(o), C.ptr(winv_t), C.ptr(noise), C.ptr(out), C.ptr(a0), m, c, early, z_col,
+           float(sigma), next_c, C.dt(a0) if a0 is not None else C.F16, C.stream())
+    return out, a0

@@ -656,6 +656,17 @@ int dle_wg_weight_norm_fwd_batched(const int64_t* table_dev, int n_entries, int6
 int dle_wg_weight_norm_bwd_batched(const int64_t* table_dev, int n_entries, int64_t total_rows, hipStream_t stream);
 int dle_wg_logdet_inv_batched(const float* base, const int64_t* table_dev, float* logdets, float* WinvT, float* signs,
                               int n_flows, hipStream_t stream);
+/* Inference, WaveGlow.infer (model.py:234-272): one launch per flow of the reverse pass on the fp32 state [M, 8].
+ * dle_wg_flow_inv: audio_1 = (audio_1 - b) * exp(-log_s) with o = (b | log_s | 0) fp32 [M, 8] from the `end` GEMM, then W^-1 on
+ *   the c active columns [8-c, 8) (WinvT as dle_wg_logdet_inv(_batched) writes it).  early > 0: columns [8-c-early, 8-c) <-
+ *   sigma * noise[:, z_col .. z_col+early), noise fp32 [M, 8] = the rows of the reference's z [B, 8, T/8].  Columns below pass
+ *   through bit for bit; out may be state.  a0_16 (optional): the first next_c/2 columns from 8-next_c of the new state, zero
+ *   padded to 8, 16-bit -- the `start` operand of the flow that runs next (the shape dle_wg_invconv_fwd emits).
+ * dle_wg_flow_inv_first: the starting state, columns [8-c, 8) = sigma * noise[:, 0 .. c), the others 0, and its a0. */
+int dle_wg_flow_inv(const float* state, const float* o, const float* WinvT, const float* noise, float* out, void* a0_16,
+                    int64_t M, int c, int early, int z_col, float sigma, int next_c, int dtype, hipStream_t stream);
+int dle_wg_flow_inv_first(const float* noise, float* out, void* a0_16, int64_t M, int c, float sigma, int dtype,
+                          hipStream_t stream);
 
 /* ---- Tacotron2 training step (csrc/tacotron2.hip): SpeechSynthesis/Tacotron2/tacotron2/model.py + loss_function.py -----------
  * dle_t2_lstm_fwd/bwd: the pointwise part of nn.LSTM / nn.LSTMCell (model.py:205-214,425-444) on gates [B, 4H] (i, f, g, o, biases
