@@ -18,14 +18,22 @@ template <int DT> __device__ __forceinline__ unsigned short dn16(float f) { retu
 // Streaming reads on this chip peak with FEW loads in flight per lane once ~1000 workgroups are resident (a read-only
 // sweep: 6.4 TB/s with 1-2 loads per lane, 4.8-5.3 with 8: tools/probes/read_bw.hip); tools/kbench/bn_bench on the
 // batch-256 ResNet-50 shapes: forward apply 2.83 -> 2.58 ms / step, backward apply 3.84 -> 3.62 with one trip, 1024 workgroups.
-static int g_bn_apply_trips = 1;       // grid-stride trips in flight of the apply kernels (1 / 2 / 4 forward, 1 / 2 / 3 backward)
-static int g_bn_apply_cap = 1024;      // workgroup cap of the apply kernels
+constexpr int BN_APPLY_CAP = 1024;      // workgroup cap of the apply kernels (one prefetched trip in flight per lane)
 
 static int cn_grid(long long items, int per_block, int cap = 2048) {
   long long g = (items + per_block - 1) / per_block;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// Grid of the BatchNorm apply kernels over total8 16-byte items: rounded up until the grid stride (grid * 256 lanes) is a
+// multiple of C8 = C/8, so a lane keeps the SAME 8 channels for its whole sweep and scale / shift live in registers.  C8 a
+// power of two <= 256 (every ResNet-50 layer) needs no rounding; workgroups past the end return at once.
+static int bn_apply_grid(long long total8, int C8) {
+  int grid = cn_grid(total8, 256, BN_APPLY_CAP);
+  while (((long long)grid * 256) % C8 != 0) ++grid;
+  return grid;
 }
 
 // ---------------------------------------------------------------- NCHW fp32 -> NHWC 16-bit (channels padded)
@@ -148,11 +156,13 @@ struct BnRedArgs {
   int lpr;                      // lanes per row = pow2 >= C/8 (<= 256)
 };
 
-// MM (MODE 1): 0 = no ReLU mask, 1 = bit mask (a.mask), 2 = saved output (a.y), -1 = decided at run time (legacy form).
-// With the mask kind a run-time pointer test, the loads of the U rows sat in conditional blocks and hipcc put s_waitcnt
-// vmcnt(0) between them (a possibly-pending load into the same registers on another path): ONE row in flight per lane.
-// The compile-time forms issue all loads of a batch back to back and request the next batch before reducing the current.
-template <int DT, int MODE, int UU = 0, int MM = -1>
+// MM (MODE 1, compile time): 0 = no ReLU mask, 1 = bit mask (a.mask), 2 = saved output (a.y).  With the mask kind a run-time
+// pointer test, the loads of a batch sat in conditional blocks and hipcc put s_waitcnt vmcnt(0) between them (a possibly-pending
+// load into the same registers on another path): ONE row in flight per lane.
+// MODE 0 keeps 8 rows in flight per lane.  MODE 1 issues the loads of a batch of 2 rows back to back and requests the next
+// batch before reducing the current (measured on the batch-256 ResNet-50 shapes with tools/kbench/bn_bench: 2 rows -> 2.5 ms /
+// step, 4 -> 3.1, 8 -> 5.5).
+template <int DT, int MODE, int MM = 0>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(BnRedArgs a) {
   __shared__ float red[2][256 * 8];
   const int cl = threadIdx.x % a.lpr, rl = threadIdx.x / a.lpr, rstep = 256 / a.lpr;
@@ -168,43 +178,24 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnRedArgs a) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) { mu[k] = a.mean[c0 + k]; rs[k] = a.rstd[c0 + k]; }
     }
-    auto accum = [&](ushort8_t xv, ushort8_t gv, ushort8_t yv, unsigned bits) {
+    auto load_row = [&](long long row, ushort8_t& xv, ushort8_t& gv, ushort8_t& yv, unsigned& mb) __attribute__((always_inline)) {
+      const long long o = row * a.C + c0;
+      xv = *(const ushort8_t*)(a.x + o);
+      mb = 0;
+      if constexpr (MODE == 1) {
+        gv = *(const ushort8_t*)(a.dy + o);
+        if constexpr (MM == 1) mb = a.mask[o >> 3];
+        if constexpr (MM == 2) yv = *(const ushort8_t*)(a.y + o);
+      }
+    };
+    auto accum = [&](ushort8_t xv, ushort8_t gv, ushort8_t yv, unsigned bits) __attribute__((always_inline)) {
       float xf[8];
       unpack8<DT>(xv, xf);
-      if (MODE == 0) {
+      if constexpr (MODE == 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) { s0[k] += xf[k]; s1[k] += xf[k] * xf[k]; }
       } else {
         float gf[8], yf[8];
-        unpack8<DT>(gv, gf);
-        if (a.y) unpack8<DT>(yv, yf);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          float g = gf[k];
-          if (a.mask ? !((bits >> k) & 1u) : (a.y && !(yf[k] > 0.f))) g = 0.f;
-          s0[k] += g;
-          s1[k] += g * (xf[k] - mu[k]) * rs[k];
-        }
-      }
-    };
-    constexpr int U = UU ? UU : (MODE == 0 ? 8 : 4);   // rows in flight per lane (U x 1..3 independent 16-byte loads)
-    long long r = r0 + rl;
-    if constexpr (MODE == 1 && MM >= 0) {
-      auto load_batch = [&](long long rb, ushort8_t (&xv)[U], ushort8_t (&gv)[U], ushort8_t (&yv)[U], unsigned (&mb)[U])
-          __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const long long o = (rb + (long long)u * rstep) * a.C + c0;
-          xv[u] = *(const ushort8_t*)(a.x + o);
-          gv[u] = *(const ushort8_t*)(a.dy + o);
-          mb[u] = 0;
-          if constexpr (MM == 1) mb[u] = a.mask[o >> 3];
-          if constexpr (MM == 2) yv[u] = *(const ushort8_t*)(a.y + o);
-        }
-      };
-      auto accum_mm = [&](ushort8_t xv, ushort8_t gv, ushort8_t yv, unsigned bits) __attribute__((always_inline)) {
-        float xf[8], gf[8], yf[8];
-        unpack8<DT>(xv, xf);
         unpack8<DT>(gv, gf);
         if constexpr (MM == 2) unpack8<DT>(yv, yf);
 #pragma unroll
@@ -215,52 +206,42 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnRedArgs a) {
           s0[k] += g;
           s1[k] += g * (xf[k] - mu[k]) * rs[k];
         }
-      };
-      const long long bstep = (long long)U * rstep;
-      if (r + (long long)(U - 1) * rstep < r1) {
-        ushort8_t xv[U], gv[U], yv[U], xn[U], gn[U], yn[U];
-        unsigned mb[U], mn[U];
-        load_batch(r, xv, gv, yv, mb);
-        for (; r + bstep + (long long)(U - 1) * rstep < r1; r += bstep) {
-          load_batch(r + bstep, xn, gn, yn, mn);
-#pragma unroll
-          for (int u = 0; u < U; ++u) accum_mm(xv[u], gv[u], yv[u], mb[u]);
-#pragma unroll
-          for (int u = 0; u < U; ++u) { xv[u] = xn[u]; gv[u] = gn[u]; yv[u] = yn[u]; mb[u] = mn[u]; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) accum_mm(xv[u], gv[u], yv[u], mb[u]);
-        r += bstep;
       }
-    } else {
-    for (; r + (long long)(U - 1) * rstep < r1; r += (long long)U * rstep) {
-      ushort8_t xv[U], gv[U], yv[U];
-      unsigned mb[U];
+    };
+    constexpr int U = MODE == 0 ? 8 : 2;   // rows per batch and lane (U x 1..3 independent 16-byte loads)
+    const long long bstep = (long long)U * rstep;
+    long long r = r0 + rl;
+    if constexpr (MODE == 0) {
+      for (; r + (long long)(U - 1) * rstep < r1; r += bstep) {
+        ushort8_t xv[U], gv[U], yv[U];
+        unsigned mb[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long o = (r + (long long)u * rstep) * a.C + c0;
-        xv[u] = *(const ushort8_t*)(a.x + o);
-        mb[u] = 0;
-        if (MODE == 1) {
-          gv[u] = *(const ushort8_t*)(a.dy + o);
-          if (a.mask) mb[u] = a.mask[o >> 3];
-          else if (a.y) yv[u] = *(const ushort8_t*)(a.y + o);
-        }
+        for (int u = 0; u < U; ++u) load_row(r + (long long)u * rstep, xv[u], gv[u], yv[u], mb[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) accum(xv[u], gv[u], yv[u], mb[u]);
+      }
+    } else if (r + (long long)(U - 1) * rstep < r1) {
+      ushort8_t xv[U], gv[U], yv[U], xn[U], gn[U], yn[U];
+      unsigned mb[U], mn[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) load_row(r + (long long)u * rstep, xv[u], gv[u], yv[u], mb[u]);
+      for (; r + bstep + (long long)(U - 1) * rstep < r1; r += bstep) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) load_row(r + bstep + (long long)u * rstep, xn[u], gn[u], yn[u], mn[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) accum(xv[u], gv[u], yv[u], mb[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) { xv[u] = xn[u]; gv[u] = gn[u]; yv[u] = yn[u]; mb[u] = mn[u]; }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) accum(xv[u], gv[u], yv[u], mb[u]);
-    }
+      r += bstep;
     }
     for (; r < r1; r += rstep) {
-      const long long o = r * a.C + c0;
-      ushort8_t gv = {}, yv = {};
-      unsigned mb = 0;
-      if (MODE == 1) {
-        gv = *(const ushort8_t*)(a.dy + o);
-        if (a.mask) mb = a.mask[o >> 3];
-        else if (a.y) yv = *(const ushort8_t*)(a.y + o);
-      }
-      accum(*(const ushort8_t*)(a.x + o), gv, yv, mb);
+      ushort8_t xv, gv = {}, yv = {};
+      unsigned mb;
+      load_row(r, xv, gv, yv, mb);
+      accum(xv, gv, yv, mb);
     }
   }
 #pragma unroll
@@ -274,6 +255,53 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnRedArgs a) {
       a.partial[((long long)blockIdx.y * 2 + 0) * a.C + c0 + k] = t0;
       a.partial[((long long)blockIdx.y * 2 + 1) * a.C + c0 + k] = t1;
     }
+  }
+}
+
+// mean, clamped biased variance -> rstd, and the running statistics (momentum, unbiased variance) like nn.BatchNorm2d, from
+// column c's sums t0 = sum x, t1 = sum x^2 over M rows.
+__device__ __forceinline__ void bn_stats_store(int c, double t0, double t1, long long M, float eps, float momentum,
+                                               float* __restrict__ mean, float* __restrict__ rstd,
+                                               float* __restrict__ running_mean, float* __restrict__ running_var) {
+  const double m = t0 / (double)M;
+  double var = t1 / (double)M - m * m;
+  if (var < 0.0) var = 0.0;
+  mean[c] = (float)m;
+  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (running_mean) {
+    const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
+  }
+}
+
+// The one-launch fold of partial rows [groups][2][C] by a workgroup of 256 lanes: 8 columns (blockIdx.x * 8 + lane % 8) x 32
+// group slices, 8 loads per stream in flight, sums in fp64, fixed order.  done(c, t0, t1) runs on the lane that holds the two
+// totals of a column c < C.
+template <class F>
+__device__ __forceinline__ void bn_fold_8x32(const float* __restrict__ partial, int groups, int C, F done) {
+  __shared__ double red[2][256];
+  const int cl = threadIdx.x & 7, sl = threadIdx.x >> 3;
+  const int c = blockIdx.x * 8 + cl;
+  double s0 = 0.0, s1 = 0.0;
+  if (c < C) {
+    int g = sl;
+    for (; g + 7 * 32 < groups; g += 8 * 32) {
+      float a[8], b[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { a[u] = partial[((long long)(g + 32 * u) * 2) * C + c]; b[u] = partial[((long long)(g + 32 * u) * 2 + 1) * C + c]; }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { s0 += a[u]; s1 += b[u]; }
+    }
+    for (; g < groups; g += 32) { s0 += partial[((long long)g * 2) * C + c]; s1 += partial[((long long)g * 2 + 1) * C + c]; }
+  }
+  red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
+  __syncthreads();
+  if (sl == 0 && c < C) {
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int q = 0; q < 32; ++q) { t0 += red[0][q * 8 + cl]; t1 += red[1][q * 8 + cl]; }
+    done(c, t0, t1);
   }
 }
 
@@ -303,16 +331,7 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const float* __res
   if (sl == 0 && c < C) {
     const double t0 = red[0][cl] + red[0][64 + cl] + red[0][128 + cl] + red[0][192 + cl];
     const double t1 = red[1][cl] + red[1][64 + cl] + red[1][128 + cl] + red[1][192 + cl];
-    const double m = t0 / (double)M;
-    double var = t1 / (double)M - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) {
-      const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
+    bn_stats_store(c, t0, t1, M, eps, momentum, mean, rstd, running_mean, running_var);
   }
 }
 
@@ -321,30 +340,10 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const float* __res
 __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const float* __restrict__ partial, int groups, int C,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                             int accumulate) {
-  __shared__ double red[2][256];
-  const int cl = threadIdx.x & 7, sl = threadIdx.x >> 3;
-  const int c = blockIdx.x * 8 + cl;
-  double s0 = 0.0, s1 = 0.0;
-  if (c < C) {
-    int g = sl;
-    for (; g + 7 * 32 < groups; g += 8 * 32) {
-      float a[8], b[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { a[u] = partial[((long long)(g + 32 * u) * 2) * C + c]; b[u] = partial[((long long)(g + 32 * u) * 2 + 1) * C + c]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s0 += a[u]; s1 += b[u]; }
-    }
-    for (; g < groups; g += 32) { s0 += partial[((long long)g * 2) * C + c]; s1 += partial[((long long)g * 2 + 1) * C + c]; }
-  }
-  red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-  __syncthreads();
-  if (sl == 0 && c < C) {
-    double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 32; ++q) { t0 += red[0][q * 8 + cl]; t1 += red[1][q * 8 + cl]; }
+  bn_fold_8x32(partial, groups, C, [&](int c, double t0, double t1) {
     dbeta[c] = accumulate ? dbeta[c] + (float)t0 : (float)t0;
     dgamma[c] = accumulate ? dgamma[c] + (float)t1 : (float)t1;
-  }
+  });
 }
 
 // level 1 of the statistics finish when the partials come from a convolution epilogue (one group per 128-row tile:
@@ -390,39 +389,12 @@ __global__ __launch_bounds__(256) void bn_stats_finish_wide_kernel(const float* 
                                                                    float* __restrict__ mean, float* __restrict__ rstd,
                                                                    float* __restrict__ running_mean,
                                                                    float* __restrict__ running_var) {
-  __shared__ double red[2][256];
-  const int cl = threadIdx.x & 7, sl = threadIdx.x >> 3;
-  const int c = blockIdx.x * 8 + cl;
-  double s0 = 0.0, s1 = 0.0;
-  if (c < C) {
-    int g = sl;
-    for (; g + 7 * 32 < groups; g += 8 * 32) {
-      float a[8], b[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { a[u] = partial[((long long)(g + 32 * u) * 2) * C + c]; b[u] = partial[((long long)(g + 32 * u) * 2 + 1) * C + c]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s0 += a[u]; s1 += b[u]; }
-    }
-    for (; g < groups; g += 32) { s0 += partial[((long long)g * 2) * C + c]; s1 += partial[((long long)g * 2 + 1) * C + c]; }
-  }
-  red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-  __syncthreads();
-  if (sl == 0 && c < C) {
-    double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 32; ++q) { t0 += red[0][q * 8 + cl]; t1 += red[1][q * 8 + cl]; }
-    const double m = t0 / (double)M;
-    double var = t1 / (double)M - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) {
-      const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-  }
+  bn_fold_8x32(partial, groups, C, [&](int c, double t0, double t1) {
+    bn_stats_store(c, t0, t1, M, eps, momentum, mean, rstd, running_mean, running_var);
+  });
 }
+
+constexpr int BN_FINISH_WIDE_MAX = 1100;   // most partial rows that bn_stats_finish_wide_kernel folds in one launch
 
 // mean / rstd / running statistics from per-group column sums [groups][2][C] (dle_conv2d_fwd_colstats);
 // workspace: >= 32 * 2 * C floats.
@@ -434,8 +406,7 @@ extern "C" int dle_bn_stats_from_partials(const float* partial, int groups, int6
   DLE_CHECK_ARG(workspace_bytes >= 32LL * 2 * C * 4, "bn_stats_from_partials: workspace too small");
   const float* src = partial;
   int g = groups;
-  static const int wide_max = getenv("DLE_BN_FINISH_WIDE") ? atoi(getenv("DLE_BN_FINISH_WIDE")) : 1100;   // 0: always fold + finish
-  if (groups > 32 && groups <= wide_max) {
+  if (groups > 32 && groups <= BN_FINISH_WIDE_MAX) {
     hipLaunchKernelGGL(bn_stats_finish_wide_kernel, dim3((C + 7) / 8), dim3(256), 0, stream, partial, groups, C, (long long)M, eps,
                        momentum, mean, rstd, running_mean, running_var);
     DLE_LAUNCH_CHECK();
@@ -453,34 +424,17 @@ extern "C" int dle_bn_stats_from_partials(const float* partial, int groups, int6
   return 0;
 }
 
-static const int g_bn_pf = getenv("DLE_BN_PF") ? atoi(getenv("DLE_BN_PF")) : 1;   // prefetched / compile-time-mode streaming kernels
-static int g_bn_want_blocks = 1024;    // ~4 workgroups per CU
-static int g_bn_bwd_u = 2;             // rows in flight per lane of the backward reduction (2 / 4 / 8); measured on the
-                                       // batch-256 ResNet-50 shapes (tools/kbench/bn_bench): 2 -> 2.5 ms / step, 4 -> 3.1, 8 -> 5.5
-static int g_bn_lpr_cap = 32;          // lanes per row: wide layers split their columns over blockIdx.x instead of
+// Geometry of the column reductions, measured on the batch-256 ResNet-50 shapes (tools/kbench/bn_bench).
+constexpr int BN_WANT_BLOCKS = 1024;   // ~4 workgroups per CU
+constexpr int BN_LPR_CAP = 32;         // lanes per row: wide layers split their columns over blockIdx.x instead of
                                        // multiplying the row groups (the partials are groups x 2 x C floats)
-
-// Tuning knobs for A/B measurements (tools/kbench/bn_bench): target workgroup count and loads in flight of the
-// reduction kernels; values <= 0 keep the current setting.
-extern "C" int dle_bn_tune_apply(int trips, int grid_cap) {
-  if (trips > 0) g_bn_apply_trips = trips;
-  if (grid_cap > 0) g_bn_apply_cap = grid_cap;
-  return 0;
-}
-
-extern "C" int dle_bn_tune(int want_blocks, int bwd_rows_in_flight) {
-  if (want_blocks >= 100000) { g_bn_lpr_cap = want_blocks / 100000; want_blocks %= 100000; }   // cap * 100000 + blocks
-  if (want_blocks > 0) g_bn_want_blocks = want_blocks;
-  if (bwd_rows_in_flight == 2 || bwd_rows_in_flight == 4 || bwd_rows_in_flight == 8) g_bn_bwd_u = bwd_rows_in_flight;
-  return 0;
-}
 
 static int bn_reduce_geometry(long long M, int C, int& lpr, int& gx, long long& rpb, long long& gy) {
   const int cols_v = C / 8;
   lpr = 1;
-  while (lpr < cols_v && lpr < g_bn_lpr_cap) lpr <<= 1;
+  while (lpr < cols_v && lpr < BN_LPR_CAP) lpr <<= 1;
   gx = (cols_v + lpr - 1) / lpr;
-  long long want = g_bn_want_blocks / gx;
+  long long want = BN_WANT_BLOCKS / gx;
   if (want < 1) want = 1;
   rpb = (M + want - 1) / want;
   const long long min_rows = 8LL * (256 / lpr);
@@ -519,70 +473,10 @@ extern "C" int dle_bn_fwd_stats(const void* x, int64_t M, int C, float eps, floa
 }
 
 // y = act( (x - mean) * rstd * gamma + beta (+ residual) ),  act = ReLU when relu != 0
-// The grid stride (gridDim * 256 lanes) is a multiple of C/8 (a power of two <= 256 ... or any divisor of the
-// stride), so a lane keeps the SAME 8 channels for its whole sweep: scale/shift live in registers.
-template <int DT, int TR>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const unsigned short* __restrict__ x,
-                                                       const unsigned short* __restrict__ res,
-                                                       unsigned short* __restrict__ y, const float* __restrict__ mean,
-                                                       const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, long long total8, int C8,
-                                                       int relu, unsigned char* __restrict__ mask_out) {
-  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const bool invariant = (stride % C8) == 0;
-  float sc[8], sh[8];
-  int c0 = (int)(first % C8) * 8;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { sc[k] = rstd[c0 + k] * gamma[c0 + k]; sh[k] = beta[c0 + k] - mean[c0 + k] * sc[k]; }
-  auto one = [&](long long i, ushort8_t xv, ushort8_t rv) {
-    float xf[8], rf[8], of[8];
-    unpack8<DT>(xv, xf);
-    if (res) unpack8<DT>(rv, rf);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float v = xf[k] * sc[k] + sh[k];
-      if (res) v += rf[k];
-      if (relu) v = v > 0.f ? v : 0.f;
-      of[k] = v;
-    }
-    ((ushort8_t*)y)[i] = pack8<DT>(of);
-    if (mask_out) {                      // ReLU mask for the backward pass: 1 bit per element instead of re-reading y
-      unsigned bits = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) bits |= (of[k] > 0.f ? 1u : 0u) << k;
-      mask_out[i] = (unsigned char)bits;
-    }
-  };
-  long long i = first;
-  if (invariant) {
-    // 4 trips in flight per lane (4-8 independent 16-byte loads): a lane alone does not cover the HBM latency
-    for (; i + (TR - 1) * stride < total8; i += TR * stride) {
-      ushort8_t xv[TR], rv[TR];
-#pragma unroll
-      for (int u = 0; u < TR; ++u) {
-        xv[u] = ((const ushort8_t*)x)[i + u * stride];
-        if (res) rv[u] = ((const ushort8_t*)res)[i + u * stride];
-      }
-#pragma unroll
-      for (int u = 0; u < TR; ++u) one(i + u * stride, xv[u], rv[u]);
-    }
-  }
-  for (; i < total8; i += stride) {
-    if (!invariant) {
-      c0 = (int)(i % C8) * 8;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { sc[k] = rstd[c0 + k] * gamma[c0 + k]; sh[k] = beta[c0 + k] - mean[c0 + k] * sc[k]; }
-    }
-    ushort8_t rv = {};
-    if (res) rv = ((const ushort8_t*)res)[i];
-    one(i, ((const ushort8_t*)x)[i], rv);
-  }
-}
-
-// The same pass with the NEXT trip's loads requested before the current trip's stores (vmcnt retires in order: a load issued
-// after a store cannot be consumed before that store is acknowledged), the residual / mask choices compile-time (no loads
-// inside run-time conditionals) and the grid stride a multiple of C/8 (the launcher checks it).
+// The grid stride (gridDim * 256 lanes) is a multiple of C/8 (bn_apply_grid), so a lane keeps the SAME 8 channels for its whole
+// sweep: scale/shift live in registers.  The NEXT trip's loads are requested before the current trip's stores (vmcnt retires in
+// order: a load issued after a store cannot be consumed before that store is acknowledged) and the residual / mask choices are
+// compile-time (no loads inside run-time conditionals).
 template <int DT, bool HAS_RES, int ACT>      // ACT: 0 = none, 1 = ReLU, 2 = ReLU + bit mask
 __global__ __launch_bounds__(256) void bn_apply_pf_kernel(const unsigned short* __restrict__ x,
                                                           const unsigned short* __restrict__ res,
@@ -645,23 +539,15 @@ extern "C" int dle_bn_fwd_apply(const void* x, const void* residual, void* y, vo
   if (M == 0) return 0;
   DLE_CHECK_ARG(x && y && mean && rstd && gamma && beta, "bn_fwd_apply: null pointer");
   const long long total8 = (long long)M * (C / 8);
-  const int grid = cn_grid(total8, 256, g_bn_apply_cap);
-#define BN_APP(DT, TR) hipLaunchKernelGGL((bn_apply_kernel<DT, TR>), dim3(grid), dim3(256), 0, stream, (const unsigned short*)x, (const unsigned short*)residual, (unsigned short*)y, mean, rstd, gamma, beta, total8, C / 8, relu, (unsigned char*)relu_mask)
-#define BN_APP_T(DT) do { if (g_bn_apply_trips == 1) BN_APP(DT, 1); else if (g_bn_apply_trips == 2) BN_APP(DT, 2); else BN_APP(DT, 4); } while (0)
-  if (g_bn_pf && ((long long)grid * 256) % (C / 8) == 0) {
-    const int act = !relu ? 0 : (relu_mask ? 2 : 1);
+  const int grid = bn_apply_grid(total8, C / 8);
+  const int act = !relu ? 0 : (relu_mask ? 2 : 1);
 #define BN_PF(DT, HR, ACT) hipLaunchKernelGGL((bn_apply_pf_kernel<DT, HR, ACT>), dim3(grid), dim3(256), 0, stream, (const unsigned short*)x, (const unsigned short*)residual, (unsigned short*)y, mean, rstd, gamma, beta, total8, C / 8, (unsigned char*)relu_mask)
 #define BN_PF_A(DT, HR) do { if (act == 0) BN_PF(DT, HR, 0); else if (act == 1) BN_PF(DT, HR, 1); else BN_PF(DT, HR, 2); } while (0)
 #define BN_PF_R(DT) do { if (residual) BN_PF_A(DT, true); else BN_PF_A(DT, false); } while (0)
-    if (dtype == DLE_F16) BN_PF_R(DLE_F16); else BN_PF_R(DLE_BF16);
+  if (dtype == DLE_F16) BN_PF_R(DLE_F16); else BN_PF_R(DLE_BF16);
 #undef BN_PF
 #undef BN_PF_A
 #undef BN_PF_R
-  } else {
-    if (dtype == DLE_F16) BN_APP_T(DLE_F16); else BN_APP_T(DLE_BF16);
-  }
-#undef BN_APP
-#undef BN_APP_T
   DLE_LAUNCH_CHECK();
   return 0;
 }
@@ -735,8 +621,7 @@ extern "C" int dle_bn_fwd_apply2(const void* x, const void* xr, void* y, void* r
   DLE_CHECK_ARG(x && xr && y && relu_mask && mean && rstd && gamma && beta && mean_r && rstd_r && gamma_r && beta_r,
                 "bn_fwd_apply2: null pointer");
   const long long total8 = (long long)M * (C / 8);
-  int grid = cn_grid(total8, 256, g_bn_apply_cap);
-  while (((long long)grid * 256) % (C / 8) != 0) ++grid;   // a lane keeps its 8 channels for the whole sweep
+  const int grid = bn_apply_grid(total8, C / 8);
   if (dtype == DLE_F16)
     hipLaunchKernelGGL((bn_apply2_pf_kernel<DLE_F16>), dim3(grid), dim3(256), 0, stream, (const unsigned short*)x, (const unsigned short*)xr,
                        (unsigned short*)y, mean, rstd, gamma, beta, mean_r, rstd_r, gamma_r, beta_r, total8, C / 8, (unsigned char*)relu_mask);
@@ -760,13 +645,10 @@ extern "C" int dle_bn_bwd_reduce(const void* dy, const void* y, const void* relu
   BnRedArgs a = {(const unsigned short*)x, (const unsigned short*)dy, (const unsigned short*)y,
                  (const unsigned char*)relu_mask, mean, rstd, (float*)workspace, (long long)M, C, rpb, lpr};
   dim3 grid(gx, (unsigned)gy), block(256);
-  const int mm = g_bn_pf ? (relu_mask ? 1 : (y ? 2 : 0)) : -1;
-#define BN_RED(DT) do { if (mm == 1) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 2, 1>), grid, block, 0, stream, a); \
-    else if (mm == 0) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 2, 0>), grid, block, 0, stream, a); \
-    else if (mm == 2) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 2, 2>), grid, block, 0, stream, a); \
-    else if (g_bn_bwd_u == 2) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 2>), grid, block, 0, stream, a); \
-    else if (g_bn_bwd_u == 8) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 8>), grid, block, 0, stream, a); \
-    else hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 4>), grid, block, 0, stream, a); } while (0)
+  const int mm = relu_mask ? 1 : (y ? 2 : 0);
+#define BN_RED(DT) do { if (mm == 1) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 1>), grid, block, 0, stream, a); \
+    else if (mm == 0) hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 0>), grid, block, 0, stream, a); \
+    else hipLaunchKernelGGL((bn_reduce_kernel<DT, 1, 2>), grid, block, 0, stream, a); } while (0)
   if (dtype == DLE_F16) BN_RED(DLE_F16); else BN_RED(DLE_BF16);
 #undef BN_RED
   DLE_LAUNCH_CHECK();
@@ -779,7 +661,7 @@ extern "C" int dle_bn_bwd_reduce(const void* dy, const void* y, const void* relu
 // The backward reduction of TWO BatchNorms that receive the same gradient: bn3 and the downsample branch's BatchNorm of a
 // bottleneck's first block both see g = dy under the block's output keep bits (out = relu(bn3(t3) + bn_ds(t_ds)),
 // models/resnet.py:166-173).  Two dle_bn_bwd_reduce launches read dy and the mask twice; this one reads them once:
-// sum g (shared), sum g xhat_1, sum g xhat_2.  Per BatchNorm the partial rows and the fold are those of bn_reduce_kernel<.., 1, 2, 1>
+// sum g (shared), sum g xhat_1, sum g xhat_2.  Per BatchNorm the partial rows and the fold are those of bn_reduce_kernel<.., 1, 1>
 // + bn_bwd_finish_kernel: the same products in the same order, results bit-identical to the two launches.
 struct BnRed2Args {
   const unsigned short* x1; const unsigned short* x2; const unsigned short* dy; const unsigned char* mask;
@@ -905,76 +787,8 @@ extern "C" int dle_bn_bwd_finish(const float* partial, int groups, int C, float*
 
 // backward pass 2: dx = gamma * rstd * (g - dbeta/M - xhat * dgamma/M), g = dy * (y > 0);
 // g_out (optional) receives g: the gradient that flows into the residual branch.
-template <int DT, int TR>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const unsigned short* __restrict__ dy,
-                                                           const unsigned short* __restrict__ y,
-                                                           const unsigned char* __restrict__ mask,
-                                                           const unsigned short* __restrict__ x,
-                                                           unsigned short* __restrict__ dx,
-                                                           unsigned short* __restrict__ g_out,
-                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                           const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                                           const float* __restrict__ dbeta, long long total8, int C8,
-                                                           float inv_m) {
-  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const bool invariant = (stride % C8) == 0;
-  // dx = a * g + b * x + c   with  a = gamma*rstd,  b = -a * rstd^2 * dgamma/M ... written per channel:
-  //   xhat = (x - mean) * rstd ;  dx = a * (g - dbeta/M - xhat * dgamma/M)
-  float ka[8], kmu[8], krs[8], kb[8], kg[8];
-  auto load = [&](int c0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      krs[k] = rstd[c0 + k];
-      kmu[k] = mean[c0 + k];
-      ka[k] = gamma[c0 + k] * krs[k];
-      kb[k] = dbeta[c0 + k] * inv_m;
-      kg[k] = dgamma[c0 + k] * inv_m;
-    }
-  };
-  load((int)(first % C8) * 8);
-  auto one = [&](long long i, ushort8_t gv, ushort8_t xv, ushort8_t yv, unsigned bits) {
-    float gf[8], xf[8], yf[8], of[8];
-    unpack8<DT>(gv, gf);
-    unpack8<DT>(xv, xf);
-    if (y) unpack8<DT>(yv, yf);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (mask ? !((bits >> k) & 1u) : (y && !(yf[k] > 0.f))) gf[k] = 0.f;
-      const float xh = (xf[k] - kmu[k]) * krs[k];
-      of[k] = ka[k] * (gf[k] - kb[k] - xh * kg[k]);
-    }
-    ((ushort8_t*)dx)[i] = pack8<DT>(of);
-    if (g_out) ((ushort8_t*)g_out)[i] = pack8<DT>(gf);
-  };
-  long long i = first;
-  if (invariant) {
-    for (; i + (TR - 1) * stride < total8; i += TR * stride) {        // TR trips = 2-3 TR independent 16-byte loads in flight
-      ushort8_t gv[TR], xv[TR], yv[TR];
-      unsigned mb[TR];
-#pragma unroll
-      for (int u = 0; u < TR; ++u) {
-        gv[u] = ((const ushort8_t*)dy)[i + u * stride];
-        xv[u] = ((const ushort8_t*)x)[i + u * stride];
-        mb[u] = 0;
-        if (mask) mb[u] = mask[i + u * stride];
-        else if (y) yv[u] = ((const ushort8_t*)y)[i + u * stride];
-      }
-#pragma unroll
-      for (int u = 0; u < TR; ++u) one(i + u * stride, gv[u], xv[u], yv[u], mb[u]);
-    }
-  }
-  for (; i < total8; i += stride) {
-    if (!invariant) load((int)(i % C8) * 8);
-    ushort8_t yv = {};
-    unsigned mb = 0;
-    if (mask) mb = mask[i];
-    else if (y) yv = ((const ushort8_t*)y)[i];
-    one(i, ((const ushort8_t*)dy)[i], ((const ushort8_t*)x)[i], yv, mb);
-  }
-}
-
-// Prefetched form of the pass above (see bn_apply_pf_kernel): MM = 0 no ReLU mask, 1 bit mask, 2 saved output.
+// Prefetched like bn_apply_pf_kernel, the mask kind compile-time: MM = 0 no ReLU mask, 1 bit mask, 2 saved output.
+//   xhat = (x - mean) * rstd ;  dx = a * (g - dbeta/M - xhat * dgamma/M)  with  a = gamma * rstd
 template <int DT, int MM, bool HAS_GOUT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_pf_kernel(const unsigned short* __restrict__ dy,
                                                               const unsigned short* __restrict__ y,
@@ -1046,23 +860,15 @@ extern "C" int dle_bn_bwd_apply(const void* dy, const void* y, const void* relu_
   DLE_CHECK_ARG(M > 0 && C > 0 && C % 8 == 0, "bn_bwd_apply: bad shape");
   DLE_CHECK_ARG(dy && x && dx && mean && rstd && gamma && dgamma && dbeta, "bn_bwd_apply: null pointer");
   const long long total8 = (long long)M * (C / 8);
-  const int grid = cn_grid(total8, 256, g_bn_apply_cap);
-#define BN_BAPP(DT, TR) hipLaunchKernelGGL((bn_bwd_apply_kernel<DT, TR>), dim3(grid), dim3(256), 0, stream, (const unsigned short*)dy, (const unsigned short*)y, (const unsigned char*)relu_mask, (const unsigned short*)x, (unsigned short*)dx, (unsigned short*)g_out, mean, rstd, gamma, dgamma, dbeta, total8, C / 8, 1.0f / (float)M)
-#define BN_BAPP_T(DT) do { if (g_bn_apply_trips == 1) BN_BAPP(DT, 1); else if (g_bn_apply_trips == 2) BN_BAPP(DT, 2); else BN_BAPP(DT, 3); } while (0)
-  if (g_bn_pf && ((long long)grid * 256) % (C / 8) == 0) {
-    const int mm = relu_mask ? 1 : (y ? 2 : 0);
+  const int grid = bn_apply_grid(total8, C / 8);
+  const int mm = relu_mask ? 1 : (y ? 2 : 0);
 #define BN_PF(DT, MMV, GO) hipLaunchKernelGGL((bn_bwd_apply_pf_kernel<DT, MMV, GO>), dim3(grid), dim3(256), 0, stream, (const unsigned short*)dy, (const unsigned short*)y, (const unsigned char*)relu_mask, (const unsigned short*)x, (unsigned short*)dx, (unsigned short*)g_out, mean, rstd, gamma, dgamma, dbeta, total8, C / 8, 1.0f / (float)M)
 #define BN_PF_M(DT, GO) do { if (mm == 0) BN_PF(DT, 0, GO); else if (mm == 1) BN_PF(DT, 1, GO); else BN_PF(DT, 2, GO); } while (0)
 #define BN_PF_G(DT) do { if (g_out) BN_PF_M(DT, true); else BN_PF_M(DT, false); } while (0)
-    if (dtype == DLE_F16) BN_PF_G(DLE_F16); else BN_PF_G(DLE_BF16);
+  if (dtype == DLE_F16) BN_PF_G(DLE_F16); else BN_PF_G(DLE_BF16);
 #undef BN_PF
 #undef BN_PF_M
 #undef BN_PF_G
-  } else {
-    if (dtype == DLE_F16) BN_BAPP_T(DLE_F16); else BN_BAPP_T(DLE_BF16);
-  }
-#undef BN_BAPP
-#undef BN_BAPP_T
   DLE_LAUNCH_CHECK();
   return 0;
 }

@@ -1059,6 +1059,78 @@ def gemm_masked_add_bnred(g2, w, m, n, k, addend, bits, t2, bits2, mean2, rstd2,
     return out
 
 
+def _bn_bwd_conv1x1(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask, reduce_done, bnred, xin=None, gw=None):
+    """bn_bwd_conv1x1_dgrad (xin is None) and bn_bwd_conv1x1_dgrad_wgrad (xin, gw given) in one body: they differ in the workspace
+    split, the C entry and the unfused continuation.  -> (dt, dx, bnred taken), dt = None in the wgrad form, or None outside the
+    kernel's envelope (nothing has been launched then)."""
+    wg = xin is not None
+    more = (xin, gw) if wg else ()
+    C.require_cuda(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask, *more)
+    k = x.shape[-1]
+    m = x.numel() // k
+    n = w.shape[-1]
+    if (m < 4096 or k != 256 or n != 64 or w.numel() != k * n or not all(t.is_contiguous() for t in (dy, x, w) + more)
+            or x.dtype not in (torch.float16, torch.bfloat16) or dy.dtype != x.dtype or w.dtype != x.dtype
+            or (wg and (xin.numel() != m * n or gw.numel() != k * n or gw.dtype != torch.float32 or xin.dtype != x.dtype))
+            or os.environ.get("DLE_CONV_BNBWD", "1") == "0"
+            or any(t is not None and t.data_ptr() % 16 for t in (dy, x, w, relu_mask) + more)):   # (a view with a storage offset)
+        return None
+    ws = _bn_ws(x.reshape(m, k))
+    act_bytes = 0.125 if relu_mask is not None else 0.0
+    relu_tag = "+relu" if relu_mask is not None else ""
+    if not reduce_done:                      # (reduce_done: the producer of dy already left dgamma / dbeta: gemm_masked_add_bnred)
+        C.annotate(bytes=float(x.numel()) * (4 + act_bytes), tag="M%dxC%d%s" % (m, k, relu_tag))
+        C.call("dle_bn_bwd_reduce", C.ptr(dy), None, C.ptr(relu_mask), C.ptr(x), C.ptr(mean), C.ptr(rstd), C.ptr(dgamma),
+               C.ptr(dbeta), m, k, 0, C.ptr(ws), ws.numel() * 4, C.dt(x), C.stream())
+    dt = None if wg else torch.empty_like(x)
+    dx = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    t2 = bits2 = mean2 = rstd2 = part = None
+    if bnred is not None and bnred[0].numel() == m * n and bnred[0].is_contiguous() and bnred[1] is not None \
+            and os.environ.get("DLE_RN50_FUSE_BNRED", "1") != "0" and os.environ.get("DLE_RN50_FUSE_BNRED2", "1") != "0":
+        t2, bits2, mean2, rstd2 = bnred[:4]
+    groups = int(C.lib().dle_conv1x1_bnbwd_groups(m)) if wg or t2 is not None else 0
+    bnred_tag = "+bnred" if t2 is not None else ""
+    if wg:
+        name = "dle_conv1x1_bnbwd_dgrad_wgrad"
+        wg_bytes = int(C.lib().dle_conv1x1_bnbwd_wgrad_workspace(m, int(t2 is not None)))
+        part_bytes = (groups * 2 * n * 4 + 15) // 16 * 16 if t2 is not None else 0
+        # ONE request for both: two requests on one stream return the same buffer, and the kernel writes both in one launch
+        buf = splitk_workspace(x.device, part_bytes + wg_bytes)
+        part = buf[:part_bytes // 4] if t2 is not None else None
+        wpart = buf[part_bytes // 4:]
+        C.annotate(bytes=float(x.numel()) * (4 + act_bytes) + (dx.numel() + xin.numel()) * 2.0
+                   + dx.numel() * (2.125 if t2 is not None else 0.0),
+                   flops=4.0 * m * n * k, tag="bn_bwd+dgrad+wgrad %dx%dx%d%s%s" % (m, n, k, relu_tag, bnred_tag))
+        args = (C.ptr(dy), C.ptr(x), C.ptr(relu_mask), C.ptr(w), C.ptr(dx), C.ptr(mean), C.ptr(rstd), C.ptr(gamma), C.ptr(dgamma),
+                C.ptr(dbeta), C.ptr(t2), C.ptr(bits2), C.ptr(mean2), C.ptr(rstd2), C.ptr(part), part_bytes, C.ptr(xin), C.ptr(gw),
+                C.ptr(wpart), wpart.numel() * 4, m, n, k, C.dt(x), C.stream())
+    else:
+        name = "dle_conv1x1_bnbwd_dgrad"
+        if t2 is not None:
+            part = splitk_workspace(x.device, groups * 2 * n * 4)
+        C.annotate(bytes=float(x.numel()) * (6 + act_bytes) + dx.numel() * (2.0 + (2.125 if t2 is not None else 0.0)),
+                   flops=2.0 * m * n * k, tag="bn_bwd+dgrad %dx%dx%d%s%s" % (m, n, k, relu_tag, bnred_tag))
+        args = (C.ptr(dy), C.ptr(x), C.ptr(relu_mask), C.ptr(w), C.ptr(dt), C.ptr(dx), C.ptr(mean), C.ptr(rstd), C.ptr(gamma),
+                C.ptr(dgamma), C.ptr(dbeta), C.ptr(t2), C.ptr(bits2), C.ptr(mean2), C.ptr(rstd2), C.ptr(part),
+                part.numel() * 4 if part is not None else 0, m, n, k, C.dt(x), C.stream())
+    rc = _timed_optional(name, getattr(C.lib(), name), args)
+    if rc > 1:
+        C.check(rc - 1000 if rc > 1000 else -1, name)
+    if rc != 1:
+        # the C side declined (a condition the envelope above cannot see, e.g. its statically cached DLE_CONV_BNBWD pin): the
+        # reduction has been launched and dgamma / dbeta are final -- continue HERE with the unfused apply + GEMM (+ weight
+        # gradient), so that a caller only ever sees None (nothing launched) or the outputs with taken = False
+        dt, _ = bn_bwd(dy, None, x, mean, rstd, gamma, dgamma, dbeta, relu_mask=relu_mask, reduce_done=True, dx_out=dt)
+        gemm(dt.view(m, k), w, m, n, k, True, False, out=dx)
+        if wg and not wgrad1x1(dt.view(m, k), xin.view(m, n), gw.view(k, n)):
+            gemm(dt.view(m, k), xin.view(m, n), k, n, m, False, False, out=gw.view(k, n),
+                 splitk=pick_splitk(k, n, m, target_blocks=1024))
+        return (None if wg else dt), dx, False
+    if t2 is not None:
+        C.call("dle_bn_bwd_finish", C.ptr(part), groups, n, C.ptr(bnred[4]), C.ptr(bnred[5]), 0, C.stream())
+    return dt, dx, t2 is not None
+
+
 def bn_bwd_conv1x1_dgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask=None, reduce_done=False, bnred=None):
     """BatchNorm backward of a conv + BN unit whose convolution is 1x1 / stride 1, with the unit's data gradient in the same
     pass: the reduction (dgamma, dbeta) as in bn_bwd, then ONE kernel that applies the backward on the operand load of
@@ -1068,49 +1140,7 @@ def bn_bwd_conv1x1_dgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask=N
     dgamma2 / dbeta2 (the caller's second unit then skips its own first pass).
     -> (dt, dx [m, N], bnred taken) or None outside the kernel's envelope (nothing has been launched then: run bn_bwd + gemm).
     (When the C side declines AFTER the reduction was launched the unfused apply + GEMM run here: same triple, taken = False.)"""
-    C.require_cuda(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask)
-    k = x.shape[-1]
-    m = x.numel() // k
-    n = w.shape[-1]
-    if (m < 4096 or k != 256 or n != 64 or w.numel() != k * n or not (dy.is_contiguous() and x.is_contiguous() and w.is_contiguous())
-            or x.dtype not in (torch.float16, torch.bfloat16) or dy.dtype != x.dtype or w.dtype != x.dtype
-            or os.environ.get("DLE_CONV_BNBWD", "1") == "0"
-            or any(t is not None and t.data_ptr() % 16 for t in (dy, x, w, relu_mask))):     # (a view with a storage offset)
-        return None
-    ws = _bn_ws(x.reshape(m, k))
-    act_bytes = 0.125 if relu_mask is not None else 0.0
-    relu_tag = "+relu" if relu_mask is not None else ""
-    if not reduce_done:                      # (reduce_done: the producer of dy already left dgamma / dbeta: gemm_masked_add_bnred)
-        C.annotate(bytes=float(x.numel()) * (4 + act_bytes), tag="M%dxC%d%s" % (m, k, relu_tag))
-        C.call("dle_bn_bwd_reduce", C.ptr(dy), None, C.ptr(relu_mask), C.ptr(x), C.ptr(mean), C.ptr(rstd), C.ptr(dgamma),
-               C.ptr(dbeta), m, k, 0, C.ptr(ws), ws.numel() * 4, C.dt(x), C.stream())
-    dt = torch.empty_like(x)
-    dx = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    t2 = bits2 = mean2 = rstd2 = part = None
-    groups = 0
-    if bnred is not None and bnred[0].numel() == m * n and bnred[0].is_contiguous() and bnred[1] is not None \
-            and os.environ.get("DLE_RN50_FUSE_BNRED", "1") != "0" and os.environ.get("DLE_RN50_FUSE_BNRED2", "1") != "0":
-        t2, bits2, mean2, rstd2 = bnred[:4]
-        groups = int(C.lib().dle_conv1x1_bnbwd_groups(m))
-        part = splitk_workspace(x.device, groups * 2 * n * 4)
-    C.annotate(bytes=float(x.numel()) * (6 + act_bytes) + dx.numel() * (2.0 + (2.125 if t2 is not None else 0.0)),
-               flops=2.0 * m * n * k, tag="bn_bwd+dgrad %dx%dx%d%s%s" % (m, n, k, relu_tag, "+bnred" if t2 is not None else ""))
-    rc = _timed_optional("dle_conv1x1_bnbwd_dgrad", C.lib().dle_conv1x1_bnbwd_dgrad,
-                         (C.ptr(dy), C.ptr(x), C.ptr(relu_mask), C.ptr(w), C.ptr(dt), C.ptr(dx), C.ptr(mean), C.ptr(rstd),
-                          C.ptr(gamma), C.ptr(dgamma), C.ptr(dbeta), C.ptr(t2), C.ptr(bits2), C.ptr(mean2), C.ptr(rstd2),
-                          C.ptr(part), part.numel() * 4 if part is not None else 0, m, n, k, C.dt(x), C.stream()))
-    if rc > 1:
-        C.check(rc - 1000 if rc > 1000 else -1, "dle_conv1x1_bnbwd_dgrad")
-    if rc != 1:
-        # the C side declined (a condition the envelope above cannot see, e.g. its statically cached DLE_CONV_BNBWD pin): the
-        # reduction has been launched and dgamma / dbeta are final -- continue HERE with the unfused apply + GEMM, so that a
-        # caller only ever sees None (nothing launched) or the (dt, dx, taken) triple
-        dt, _ = bn_bwd(dy, None, x, mean, rstd, gamma, dgamma, dbeta, relu_mask=relu_mask, reduce_done=True, dx_out=dt)
-        gemm(dt.view(m, k), w, m, n, k, True, False, out=dx)
-        return dt, dx, False
-    if t2 is not None:
-        C.call("dle_bn_bwd_finish", C.ptr(part), groups, n, C.ptr(bnred[4]), C.ptr(bnred[5]), 0, C.stream())
-    return dt, dx, t2 is not None
+    return _bn_bwd_conv1x1(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask, reduce_done, bnred)
 
 
 def bn_bwd_conv1x1_dgrad_wgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, xin, gw, relu_mask=None, reduce_done=False, bnred=None):
@@ -1121,57 +1151,8 @@ def bn_bwd_conv1x1_dgrad_wgrad(dy, x, mean, rstd, gamma, dgamma, dbeta, w, xin, 
     -> (dx [m, N], bnred taken) or None outside the kernel's envelope (nothing has been launched then).
     (When the C side declines AFTER the reduction was launched the unfused apply + GEMM + weight gradient run here: same pair,
     taken = False.)"""
-    C.require_cuda(dy, x, mean, rstd, gamma, dgamma, dbeta, w, xin, gw, relu_mask)
-    k = x.shape[-1]
-    m = x.numel() // k
-    n = w.shape[-1]
-    if (m < 4096 or k != 256 or n != 64 or w.numel() != k * n or xin.numel() != m * n or gw.numel() != k * n
-            or gw.dtype != torch.float32
-            or not (dy.is_contiguous() and x.is_contiguous() and w.is_contiguous() and xin.is_contiguous() and gw.is_contiguous())
-            or x.dtype not in (torch.float16, torch.bfloat16) or dy.dtype != x.dtype or w.dtype != x.dtype or xin.dtype != x.dtype
-            or os.environ.get("DLE_CONV_BNBWD", "1") == "0"
-            or any(t is not None and t.data_ptr() % 16 for t in (dy, x, w, xin, gw, relu_mask))):
-        return None
-    ws = _bn_ws(x.reshape(m, k))
-    act_bytes = 0.125 if relu_mask is not None else 0.0
-    relu_tag = "+relu" if relu_mask is not None else ""
-    if not reduce_done:
-        C.annotate(bytes=float(x.numel()) * (4 + act_bytes), tag="M%dxC%d%s" % (m, k, relu_tag))
-        C.call("dle_bn_bwd_reduce", C.ptr(dy), None, C.ptr(relu_mask), C.ptr(x), C.ptr(mean), C.ptr(rstd), C.ptr(dgamma),
-               C.ptr(dbeta), m, k, 0, C.ptr(ws), ws.numel() * 4, C.dt(x), C.stream())
-    dx = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    t2 = bits2 = mean2 = rstd2 = None
-    if bnred is not None and bnred[0].numel() == m * n and bnred[0].is_contiguous() and bnred[1] is not None \
-            and os.environ.get("DLE_RN50_FUSE_BNRED", "1") != "0" and os.environ.get("DLE_RN50_FUSE_BNRED2", "1") != "0":
-        t2, bits2, mean2, rstd2 = bnred[:4]
-    groups = int(C.lib().dle_conv1x1_bnbwd_groups(m))
-    wg_bytes = int(C.lib().dle_conv1x1_bnbwd_wgrad_workspace(m, int(t2 is not None)))
-    part_bytes = (groups * 2 * n * 4 + 15) // 16 * 16 if t2 is not None else 0
-    # ONE request for both: two requests on one stream return the same buffer, and the kernel writes both in one launch
-    buf = splitk_workspace(x.device, part_bytes + wg_bytes)
-    part = buf[:part_bytes // 4] if t2 is not None else None
-    wpart = buf[part_bytes // 4:]
-    C.annotate(bytes=float(x.numel()) * (4 + act_bytes) + (dx.numel() + xin.numel()) * 2.0
-               + dx.numel() * (2.125 if t2 is not None else 0.0),
-               flops=4.0 * m * n * k, tag="bn_bwd+dgrad+wgrad %dx%dx%d%s%s" % (m, n, k, relu_tag, "+bnred" if t2 is not None else ""))
-    rc = _timed_optional("dle_conv1x1_bnbwd_dgrad_wgrad", C.lib().dle_conv1x1_bnbwd_dgrad_wgrad,
-                         (C.ptr(dy), C.ptr(x), C.ptr(relu_mask), C.ptr(w), C.ptr(dx), C.ptr(mean), C.ptr(rstd),
-                          C.ptr(gamma), C.ptr(dgamma), C.ptr(dbeta), C.ptr(t2), C.ptr(bits2), C.ptr(mean2), C.ptr(rstd2),
-                          C.ptr(part), part_bytes, C.ptr(xin), C.ptr(gw), C.ptr(wpart), wpart.numel() * 4, m, n, k, C.dt(x),
-                          C.stream()))
-    if rc > 1:
-        C.check(rc - 1000 if rc > 1000 else -1, "dle_conv1x1_bnbwd_dgrad_wgrad")
-    if rc != 1:
-        # the C side declined with the reduction launched and dgamma / dbeta final: finish HERE, unfused
-        dt, _ = bn_bwd(dy, None, x, mean, rstd, gamma, dgamma, dbeta, relu_mask=relu_mask, reduce_done=True)
-        gemm(dt.view(m, k), w, m, n, k, True, False, out=dx)
-        if not wgrad1x1(dt.view(m, k), xin.view(m, n), gw.view(k, n)):
-            gemm(dt.view(m, k), xin.view(m, n), k, n, m, False, False, out=gw.view(k, n),
-                 splitk=pick_splitk(k, n, m, target_blocks=1024))
-        return dx, False
-    if t2 is not None:
-        C.call("dle_bn_bwd_finish", C.ptr(part), groups, n, C.ptr(bnred[4]), C.ptr(bnred[5]), 0, C.stream())
-    return dx, t2 is not None
+    out = _bn_bwd_conv1x1(dy, x, mean, rstd, gamma, dgamma, dbeta, w, relu_mask, reduce_done, bnred, xin, gw)
+    return out and out[1:]
 
 
 def maxpool_fwd(x, ksize=3, stride=2, pad=1):

@@ -10,8 +10,10 @@ as bit-identical to these, so this file is what ties the whole BatchNorm chain t
 
 computed by torch in float64 on the GPU (torch's own kernels, not this library's).  The (M, C) cases are the batch-256 families
 (802816, 64), (802816, 256), (200704, 128), (200704, 512), (50176, 256), (50176, 1024), (12544, 2048) and ragged ones: M a prime
-one to eight rows past a row-group boundary, C = 24, 72 (C / 8 does not divide the apply grid: the non-prefetched apply kernels),
-520 (65 column lanes over three 32-lane column blocks, the last one holding a single lane).  They reach 197 ... 1024 row groups
+one to eight rows past a row-group boundary, C = 24, 72 (C / 8 does not divide the apply grid of 1024 workgroups: the launchers
+round the grid up until it does), 520 (65 column lanes over three 32-lane column blocks, the last one holding a single lane), and
+M = 3 rows of C = 520, where the rounded-up apply grid (65 workgroups) is larger than the work (195 items: workgroups 1 ... 64
+must return at once).  They reach 197 ... 1024 row groups
 of the reduction with its 8-row batches and remainder loop, the lanes-per-row cap (C = 1024, 2048), and 1 ... 25 grid-stride
 trips of the apply kernels with the peeled first and partial last trip.
 
@@ -46,7 +48,7 @@ channel, so y is an exact shifted copy of x, zero where the tap reads padding: y
 statistics of the stored y are exact as above (the halo kernel's computed-and-dropped padding slots must not enter them).  Which
 kernel took the launch is asserted from the partial-row count dle_conv2d_fwd_colstats reports and gemm8's launch counter.
 
-DLE_BN_PF and DLE_BN_FINISH_WIDE are read once per process; this file covers the default dispatch.
+Every stand-alone pass has ONE kernel and a fixed launch geometry (no tuning knobs): this file covers all of its dispatch.
 """
 import ctypes
 
@@ -405,6 +407,13 @@ def test_fwd_apply(cuda, dtype, m, c, vid, has_res, relu, bits):
         assert torch.equal(_unpack_bits(mask, m * c), (y > 0).reshape(-1)), "keep bits != y > 0"
 
 
+@pytest.mark.parametrize("vid, has_res, relu, bits", APPLY_VARIANTS, ids=[v[0] for v in APPLY_VARIANTS])
+def test_fwd_apply_grid_larger_than_work(cuda, vid, has_res, relu, bits):
+    """M C / 8 = 195 items < one workgroup, C / 8 = 65: the grid is rounded up from 1 to 65 workgroups (65 * 256 lanes is the
+    first multiple of 65) and all but the first lie past the end.  The sentinel tails of _apply catch any write of theirs."""
+    test_fwd_apply(cuda, BF, 3, 520, vid, has_res, relu, bits)
+
+
 APPLY2_CASES = [(BF, 802816, 256), (BF, 200704, 512), (BF, 50176, 1024), (BF, 12544, 2048), (BF, 150089, 72), (HF, 50176, 1024)]
 
 
@@ -483,6 +492,12 @@ def test_bwd(cuda, dtype, m, c, mm):
     if mm == "mask":
         _bwd_reduce(dy, y, mask, x, mean, rstd, dgamma, dbeta, 1)
         assert torch.equal(dbeta, (2 * ref_dbeta).float()) and torch.equal(dgamma, (2 * ref_dgamma).float()), "accumulate=1"
+
+
+@pytest.mark.parametrize("mm", BWD_MODES)
+def test_bwd_apply_grid_larger_than_work(cuda, mm):
+    """The backward apply on the shape of test_fwd_apply_grid_larger_than_work: 65 workgroups for 195 items."""
+    test_bwd(cuda, BF, 3, 520, mm)
 
 
 @pytest.mark.parametrize("c", [64, 520, 2048])
