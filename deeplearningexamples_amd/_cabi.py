@@ -221,6 +221,10 @@ _SIGS = {
                                      c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_float, c_int, c_int, c_int, c_int,
                                      c_void_p]),
     "dle_t2_mask_rows": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_float, c_int, c_void_p]),
+    "dle_t2_prenet_infer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_u64, c_void_p, c_int, c_int,
+                                    c_int, c_int, c_void_p]),
+    "dle_t2_frame_infer": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 7 + [c_int, c_float, c_int, c_i64, c_void_p,
+                                   c_void_p, c_void_p, c_i64, c_u64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

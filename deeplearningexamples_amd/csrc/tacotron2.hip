@@ -12,6 +12,7 @@
 // (sample, unit) for the cells, one workgroup per sample for the attention (wave64 shuffle reductions over channels).
 #include <type_traits>
 #include "gemm_tiles.h"
+#include "dropout.h"
 
 #define T2_BLOCK 256
 
@@ -817,6 +818,271 @@ extern "C" int dle_t2_mel_loss(const float* out_all, int64_t ld_out, const void*
   T2_GO(t2_mel_loss_kernel, G, 0, out_all, (long long)ld_out, (const unsigned short*)post, target, scale_dev, (unsigned short*)d_out,
         (long long)ld_dout, (unsigned short*)d_post, workspace, (long long)R, n_mel);
   hipLaunchKernelGGL(t2_sum_kernel, dim3(1), dim3(T2_BLOCK), 0, stream, (const float*)workspace, G, loss);
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+// =============================================================================================== inference (Decoder.infer)
+// The free-running decoder step of tacotron2/model.py:515-595 around the existing cell / query / attention launches:
+//   t2i_prenet  Prenet.forward (model.py:124-135) for the few rows of ONE step: relu(x W0^T) -> dropout -> relu(. W1^T) -> dropout,
+//               written 16-bit into the prenet columns of the attention LSTM's operand buffer.  The dropout stays on at inference
+//               (model.py:129).  RNG contract: the keep mask of step t (0-based), layer l, over the row-major [B, P] block is the
+//               dropout.h stream of (seed, call offset 1 + 2 t + l), p = 0.5; t is read from a DEVICE word, so a replayed graph
+//               draws fresh masks.
+//   t2i_frame   linear_projection + gate_layer on [decoder_hidden | context], the stop bookkeeping of model.py:578-582 and the
+//               step counter, all on the device.
+// Few rows (B <= 8), weights of 40 KB - 250 KB: one wavefront per output column, all rows of the batch in registers, 16-byte weight
+// loads, the activations in LDS.  Rounding points are the trainer's: the frame, both prenet layers and the LSTM operands are kept
+// in 16 bits, products accumulate in fp32.
+// state (int64 [4], device): [0] / [1] the step index as seen by even / odd steps (a launch of parity p reads [p] and the frame
+// launch writes [1 - p]: no launch reads a word another workgroup of the same launch writes), [2] n_steps, [3] all samples finished.
+#define T2I_MAXB 8
+
+template <int DT> __device__ __forceinline__ float t2i_round(float v) { return Elem<DT>::to_f32(Elem<DT>::from_f32(v)); }
+
+// x: fp32 [B, NM] in global memory or LDS (NULL: the go frame, zeros).  sm: B*NM + B*P floats + 2*B*P/8 bytes.  Workgroup `part` of
+// `nparts` writes its share of the second layer's columns; every workgroup forms the whole first layer (40 KB of weights).
+template <int DT>
+__device__ void t2i_prenet(const float* x, const unsigned short* __restrict__ w0, const unsigned short* __restrict__ w1,
+                           unsigned short* __restrict__ dst, long long ld_dst, unsigned char* m0_out, unsigned char* m1_out,
+                           DropArgs d, long long step, int B, int NM, int P, float* sm, int part, int nparts) {
+  const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
+  float* xs = sm;
+  float* h1 = xs + B * NM;
+  unsigned char* mk = (unsigned char*)(h1 + B * P);
+  const int nch = B * P / 8;
+  for (int i = tid; i < B * NM; i += nt) xs[i] = x ? t2i_round<DT>(x[i]) : 0.f;
+  for (int i = tid; i < 2 * nch; i += nt) {
+    const int l = i >= nch ? 1 : 0;
+    DropArgs dl = d;
+    const unsigned long long o = (((unsigned long long)d.off_hi << 32) | d.off_lo) + 2ull * (unsigned long long)step + l;
+    dl.off_lo = (unsigned)o;
+    dl.off_hi = (unsigned)(o >> 32);
+    mk[i] = (unsigned char)drop_bits(dl, i - l * nch);
+  }
+  __syncthreads();
+  if (part == 0) {
+    for (int i = tid; i < nch; i += nt) {
+      if (m0_out) m0_out[i] = mk[i];
+      if (m1_out) m1_out[i] = mk[nch + i];
+    }
+  }
+  for (int j = tid; j < P; j += nt) {
+    float acc[T2I_MAXB];
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) acc[b] = 0.f;
+    const unsigned short* wr = w0 + (long long)j * NM;
+    for (int k = 0; k < NM; k += 8) {
+      float wf[8];
+      unpack8<DT>(*(const ushort8_t*)(wr + k), wf);
+#pragma unroll
+      for (int b = 0; b < T2I_MAXB; ++b) {
+        if (b < B) {
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc[b] += wf[r] * xs[b * NM + k + r];
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) {
+      if (b < B) {
+        const float v = t2i_round<DT>(fmaxf(acc[b], 0.f));
+        const bool keep = (mk[(b * P + j) >> 3] >> (j & 7)) & 1;
+        h1[b * P + j] = keep ? t2i_round<DT>(v * d.inv_keep) : 0.f;
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = part * nw + wave; j < P; j += nparts * nw) {
+    float acc[T2I_MAXB];
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) acc[b] = 0.f;
+    for (int k = lane * 8; k < P; k += 512) {
+      float wf[8];
+      unpack8<DT>(*(const ushort8_t*)(w1 + (long long)j * P + k), wf);
+#pragma unroll
+      for (int b = 0; b < T2I_MAXB; ++b) {
+        if (b < B) {
+          float hv[8];
+          t2_ld8f(h1 + b * P + k, hv);
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc[b] += wf[r] * hv[r];
+        }
+      }
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) {
+      if (b < B) {
+        const float s = wave_sum(acc[b]);
+        if (lane == b) mine = s;
+      }
+    }
+    if (lane < B) {
+      const float v = t2i_round<DT>(fmaxf(mine, 0.f));
+      const bool keep = (mk[nch + ((lane * P + j) >> 3)] >> (j & 7)) & 1;
+      t2_st<DT>(dst + lane * ld_dst + j, keep ? v * d.inv_keep : 0.f);
+    }
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void t2i_prenet_kernel(const float* __restrict__ x, const unsigned short* __restrict__ w0,
+                                                         const unsigned short* __restrict__ w1, unsigned short* __restrict__ dst,
+                                                         long long ld_dst, unsigned char* m0, unsigned char* m1, DropArgs d,
+                                                         const long long* __restrict__ step, int B, int NM, int P) {
+  extern __shared__ float sm[];
+  t2i_prenet<DT>(x, w0, w1, dst, ld_dst, m0, m1, d, *step, B, NM, P, sm, blockIdx.x, gridDim.x);
+}
+
+struct T2IFrameArgs {
+  const unsigned short* hc; long long ld_hc;       // [B, K] = [decoder_hidden | context]
+  const unsigned short* w; long long ldw;          // [NM + 1, K]: linear_projection rows, then the gate layer's row
+  const float* bias;                               // [NM + 1]
+  float* mel_out;                                  // [B, out_steps, NM]
+  float* gate_out;                                 // [B, out_steps]
+  float* frame_next;                               // [B, NM]: the next step's prenet input
+  int* not_finished; int* mel_lengths;             // [B]
+  long long* state;                                // [4], see above
+  int parity; float thr; int max_steps; long long out_steps;
+  const unsigned short* w0; const unsigned short* w1; unsigned short* pre_dst; long long ld_pre; DropArgs d;   // FUSED only
+  int B, NM, K, P;
+};
+
+// One wavefront per output column n (n < NM: mel channel, n == NM: the gate logit), all B rows in registers; hc sits in LDS.
+// FUSED (one workgroup): the frame stays in LDS and the NEXT step's prenet runs behind it in the same launch.
+template <int DT, bool FUSED>
+__global__ __launch_bounds__(FUSED ? 1024 : 256) void t2i_frame_kernel(T2IFrameArgs a) {
+  extern __shared__ float sm[];
+  const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
+  const int B = a.B, NM = a.NM, K = a.K;
+  unsigned short* hs = (unsigned short*)sm;                     // [B][K]
+  float* fr = sm + (B * K + 1) / 2;                             // FUSED: [B][NM]
+  const long long t = a.state[a.parity];
+  const bool valid = t >= 0 && t < a.max_steps && t < a.out_steps;
+  for (int i = tid * 8; i < B * K; i += nt * 8) {
+    const int b = i / K, k = i - b * K;
+    *(ushort8_t*)(hs + i) = *(const ushort8_t*)(a.hc + b * a.ld_hc + k);
+  }
+  __syncthreads();
+  for (int n = blockIdx.x * nw + wave; n <= NM; n += gridDim.x * nw) {
+    float acc[T2I_MAXB];
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) acc[b] = 0.f;
+    for (int k = lane * 8; k < K; k += 512) {
+      float wf[8];
+      unpack8<DT>(*(const ushort8_t*)(a.w + n * a.ldw + k), wf);
+#pragma unroll
+      for (int b = 0; b < T2I_MAXB; ++b) {
+        if (b < B) {
+          float hv[8];
+          unpack8<DT>(*(const ushort8_t*)(hs + b * K + k), hv);
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc[b] += wf[r] * hv[r];
+        }
+      }
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int b = 0; b < T2I_MAXB; ++b) {
+      if (b < B) {
+        const float s = wave_sum(acc[b]);
+        if (lane == b) mine = s;
+      }
+    }
+    const float v = mine + a.bias[n];
+    if (n < NM) {
+      if (lane < B) {
+        if (valid) a.mel_out[((long long)lane * a.out_steps + t) * NM + n] = v;
+        a.frame_next[lane * NM + n] = v;
+        if (FUSED) fr[lane * NM + n] = v;
+      }
+    } else {
+      // model.py:578-582: dec = sigmoid(gate) <= threshold; not_finished *= dec; mel_lengths += not_finished
+      int nf = 0;
+      if (lane < B && valid) {
+        a.gate_out[(long long)lane * a.out_steps + t] = v;
+        const int dec = (1.0f / (1.0f + expf(-v))) <= a.thr ? 1 : 0;
+        nf = a.not_finished[lane] * dec;
+        a.not_finished[lane] = nf;
+        a.mel_lengths[lane] += nf;
+      }
+      const float live = wave_sum((float)nf);
+      if (lane == 0) {
+        if (valid && a.state[3] == 0) {
+          a.state[2] = t + 1;
+          if (live == 0.f) a.state[3] = 1;
+        }
+        a.state[1 - a.parity] = t + 1;
+      }
+    }
+  }
+  if (FUSED) {
+    __syncthreads();
+    t2i_prenet<DT>(fr, a.w0, a.w1, a.pre_dst, a.ld_pre, nullptr, nullptr, a.d, t + 1, B, NM, a.P, fr + B * NM, 0, 1);
+  }
+}
+
+static size_t t2i_prenet_lds(int B, int NM, int P) { return ((size_t)B * NM + (size_t)B * P) * 4 + (size_t)2 * B * P / 8; }
+
+extern "C" int dle_t2_prenet_infer(const float* frame, const void* w0, const void* w1, void* dst, int64_t ld_dst, void* mask0,
+                                   void* mask1, uint64_t seed, const int64_t* step_dev, int B, int NM, int P, int dtype,
+                                   hipStream_t stream) {
+  DLE_CHECK_ARG(w0 && w1 && dst && step_dev && B > 0 && NM > 0 && P > 0, "t2_prenet_infer: bad args");
+  DLE_CHECK_ARG(B <= T2I_MAXB, "t2_prenet_infer: at most %d rows (got %d)", T2I_MAXB, B);
+  DLE_CHECK_ARG(NM % 8 == 0 && P % 8 == 0 && ld_dst >= P, "t2_prenet_infer: n_mel and prenet_dim multiples of 8, ld_dst >= prenet_dim");
+  DLE_CHECK_ARG(((((uintptr_t)w0) | ((uintptr_t)w1)) & 15) == 0 && (((uintptr_t)frame) & 3) == 0 && (((uintptr_t)step_dev) & 7) == 0,
+                "t2_prenet_infer: 16-byte aligned weights");
+  T2_DT_CHECK("t2_prenet_infer");
+  const size_t lds = t2i_prenet_lds(B, NM, P);
+  DLE_CHECK_ARG(lds <= 64 * 1024, "t2_prenet_infer: prenet_dim too large for one workgroup's LDS");
+  const DropArgs d = make_drop(nullptr, 0.5f, seed, 1);
+  int grid = (P + 15) / 16;                                  // 4 wavefronts per workgroup, 4 columns each
+  if (grid > 64) grid = 64;
+#define T2I_PRE(DT)                                                                                                              \
+    hipLaunchKernelGGL(t2i_prenet_kernel<DT>, dim3(grid), dim3(256), lds, stream, frame, (const unsigned short*)w0,              \
+                       (const unsigned short*)w1, (unsigned short*)dst, (long long)ld_dst, (unsigned char*)mask0,                \
+                       (unsigned char*)mask1, d, (const long long*)step_dev, B, NM, P)
+  if (dtype == DLE_F16) T2I_PRE(DLE_F16); else T2I_PRE(DLE_BF16);
+#undef T2I_PRE
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dle_t2_frame_infer(const void* hc, int64_t ld_hc, const void* w, int64_t ldw, const float* bias, float* mel_out,
+                                  float* gate_out, float* frame_next, int32_t* not_finished, int32_t* mel_lengths, int64_t* state,
+                                  int parity, float gate_threshold, int max_steps, int64_t out_steps, const void* w0, const void* w1,
+                                  void* pre_dst, int64_t ld_pre, uint64_t seed, int B, int NM, int K, int P, int dtype,
+                                  hipStream_t stream) {
+  DLE_CHECK_ARG(hc && w && bias && mel_out && gate_out && frame_next && not_finished && mel_lengths && state && B > 0 && NM > 0 && K > 0,
+                "t2_frame_infer: bad args");
+  DLE_CHECK_ARG(B <= T2I_MAXB, "t2_frame_infer: at most %d rows (got %d)", T2I_MAXB, B);
+  DLE_CHECK_ARG((parity == 0 || parity == 1) && max_steps > 0 && out_steps > 0, "t2_frame_infer: parity 0 / 1, positive step counts");
+  DLE_CHECK_ARG(NM % 8 == 0 && K % 8 == 0 && ld_hc % 8 == 0 && ldw % 8 == 0 && ld_hc >= K && ldw >= K &&
+                ((((uintptr_t)hc) | ((uintptr_t)w)) & 15) == 0 && (((uintptr_t)state) & 7) == 0,
+                "t2_frame_infer: n_mel, K and the row pitches multiples of 8, 16-byte aligned operands");
+  T2_DT_CHECK("t2_frame_infer");
+  const bool fused = w0 != nullptr;
+  DLE_CHECK_ARG(!fused || (w1 && pre_dst && P > 0 && P % 8 == 0 && ld_pre >= P && ((((uintptr_t)w0) | ((uintptr_t)w1)) & 15) == 0),
+                "t2_frame_infer: the fused prenet needs both weights, a destination and prenet_dim %% 8 == 0");
+  T2IFrameArgs a;
+  a.hc = (const unsigned short*)hc; a.ld_hc = ld_hc; a.w = (const unsigned short*)w; a.ldw = ldw; a.bias = bias;
+  a.mel_out = mel_out; a.gate_out = gate_out; a.frame_next = frame_next; a.not_finished = not_finished; a.mel_lengths = mel_lengths;
+  a.state = (long long*)state; a.parity = parity; a.thr = gate_threshold; a.max_steps = max_steps; a.out_steps = out_steps;
+  a.w0 = (const unsigned short*)w0; a.w1 = (const unsigned short*)w1; a.pre_dst = (unsigned short*)pre_dst; a.ld_pre = ld_pre;
+  a.d = make_drop(nullptr, 0.5f, seed, 1);
+  a.B = B; a.NM = NM; a.K = K; a.P = fused ? P : 0;
+  size_t lds = (size_t)((B * K + 1) / 2) * 4;
+  if (fused) lds += (size_t)B * NM * 4 + t2i_prenet_lds(B, NM, P);
+  DLE_CHECK_ARG(lds <= 64 * 1024, "t2_frame_infer: K too large for one workgroup's LDS");
+  if (fused) {
+    if (dtype == DLE_F16) hipLaunchKernelGGL((t2i_frame_kernel<DLE_F16, true>), dim3(1), dim3(1024), lds, stream, a);
+    else hipLaunchKernelGGL((t2i_frame_kernel<DLE_BF16, true>), dim3(1), dim3(1024), lds, stream, a);
+  } else {
+    const int grid = (NM + 1 + 3) / 4;                       // one output column per wavefront
+    if (dtype == DLE_F16) hipLaunchKernelGGL((t2i_frame_kernel<DLE_F16, false>), dim3(grid), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL((t2i_frame_kernel<DLE_BF16, false>), dim3(grid), dim3(256), lds, stream, a);
+  }
   DLE_LAUNCH_CHECK();
   return 0;
 }

@@ -151,3 +151,52 @@ def mask_rows(x, cols, lengths, b, to, value):
     if lengths.dtype != torch.int64 or lengths.numel() != b or x.shape[0] != b * to or x.shape[1] < cols or x.stride(1) != 1:
         raise ValueError("mask_rows: x [B*To, >= cols] with unit column stride, int64 lengths [B]")
     C.call("dle_t2_mask_rows", C.ptr(x), x.stride(0), cols, C.ptr(lengths), b, to, float(value), C.dt(x), C.stream())
+
+
+def prenet_infer(frame, w0, w1, dst, seed, step_word, mask0=None, mask1=None):
+    """Both prenet layers of ONE free-running decoder step with the dropout that stays on at inference (statement and RNG
+    contract: include/dle_mi355x.h, dle_t2_prenet_infer).  frame fp32 [B, n_mel] or None (the go frame); w0 [P, n_mel], w1 [P, P]
+    16-bit; dst 16-bit [B, P] row-strided view; step_word: int64 device view whose first element is the step index."""
+    C.require_cuda(frame, w0, w1, dst, step_word, mask0, mask1)
+    b, p = dst.shape
+    nm = w0.shape[1]
+    if w0.shape != (p, nm) or w1.shape != (p, p) or not (w0.is_contiguous() and w1.is_contiguous()):
+        raise ValueError("prenet_infer: contiguous weights [P, n_mel] and [P, P]")
+    if frame is not None and (frame.shape != (b, nm) or frame.dtype != torch.float32 or not frame.is_contiguous()):
+        raise ValueError("prenet_infer: the frame is contiguous fp32 [B, n_mel]")
+    if step_word.dtype != torch.int64:
+        raise ValueError("prenet_infer: the step word is int64")
+    for m in (mask0, mask1):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() != b * p // 8 or not m.is_contiguous()):
+            raise ValueError("prenet_infer: keep masks are uint8 [B * P / 8]")
+    C.call("dle_t2_prenet_infer", C.ptr(frame), C.ptr(w0), C.ptr(w1), C.ptr(dst), _ld(dst, "dst"), C.ptr(mask0), C.ptr(mask1),
+           int(seed), C.ptr(step_word), b, nm, p, C.dt(dst), C.stream())
+
+
+def frame_infer(hc, w, bias, mel_out, gate_out, frame_next, not_finished, mel_lengths, state, parity, gate_threshold, max_steps,
+                prenet=None, seed=0):
+    """The tail of one free-running decoder step: mel frame + gate logit, the stop bookkeeping and the step counter on the device
+    (include/dle_mi355x.h, dle_t2_frame_infer).  hc 16-bit [B, K]; w 16-bit [>= n_mel + 1, K]; bias fp32 [>= n_mel + 1]; mel_out fp32
+    [B, steps, n_mel]; gate_out fp32 [B, steps]; frame_next fp32 [B, n_mel]; not_finished / mel_lengths int32 [B]; state int64 [4].
+    prenet = (w0, w1, dst): the prenet of the NEXT step runs behind the frame in the same (one-workgroup) launch."""
+    w0, w1, dst = prenet if prenet is not None else (None, None, None)
+    C.require_cuda(hc, w, bias, mel_out, gate_out, frame_next, not_finished, mel_lengths, state, w0, w1, dst)
+    b, k = hc.shape
+    steps, nm = mel_out.shape[1], mel_out.shape[2]
+    if w.shape[0] < nm + 1 or w.shape[1] != k or bias.numel() < nm + 1 or bias.dtype != torch.float32:
+        raise ValueError("frame_infer: w [>= n_mel + 1, K] and fp32 bias [>= n_mel + 1]")
+    if (mel_out.shape[0] != b or not mel_out.is_contiguous() or mel_out.dtype != torch.float32 or gate_out.shape != (b, steps)
+            or not gate_out.is_contiguous() or gate_out.dtype != torch.float32 or frame_next.shape != (b, nm)
+            or not frame_next.is_contiguous() or frame_next.dtype != torch.float32):
+        raise ValueError("frame_infer: contiguous fp32 mel_out [B, steps, n_mel], gate_out [B, steps], frame_next [B, n_mel]")
+    for t in (not_finished, mel_lengths):
+        if t.dtype != torch.int32 or t.numel() != b or not t.is_contiguous():
+            raise ValueError("frame_infer: not_finished / mel_lengths are int32 [B]")
+    if state.dtype != torch.int64 or state.numel() != 4 or not state.is_contiguous():
+        raise ValueError("frame_infer: state is int64 [4]")
+    if dst is not None and (dst.shape[0] != b or w0.shape != (dst.shape[1], nm) or w1.shape != (dst.shape[1],) * 2):
+        raise ValueError("frame_infer: fused prenet weights [P, n_mel], [P, P] and a [B, P] destination")
+    C.call("dle_t2_frame_infer", C.ptr(hc), _ld(hc, "hc"), C.ptr(w), _ld(w, "w"), C.ptr(bias), C.ptr(mel_out), C.ptr(gate_out),
+           C.ptr(frame_next), C.ptr(not_finished), C.ptr(mel_lengths), C.ptr(state), int(parity), float(gate_threshold),
+           int(max_steps), steps, C.ptr(w0), C.ptr(w1), C.ptr(dst), _ld(dst, "prenet dst") if dst is not None else 0, int(seed),
+           b, nm, k, dst.shape[1] if dst is not None else 0, C.dt(hc), C.stream())

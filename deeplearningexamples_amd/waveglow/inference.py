@@ -3,8 +3,8 @@
     python -m deeplearningexamples_amd.waveglow.inference --waveglow out/checkpoint_WaveGlow_last.pt --mel mel.pt -o audio/
     python -m deeplearningexamples_amd.waveglow.inference --waveglow CKPT --synth-data -o audio/ --fp16
 
-The flag names are the reference's (inference.py:46-77); --mel / --synth-data replace its text input, because the text-to-mel
-half (Tacotron2's autoregressive infer) is not built: -i / --tacotron2 parse and exit saying so.  The checkpoint is the file
+The flag names are the reference's (inference.py:46-77); --mel / --synth-data replace its text input: the text-to-mel half lives
+in tacotron2/inference.py (text -> mel -> audio), and -i / --tacotron2 parse here only to exit pointing at it.  The checkpoint is the file
 waveglow/train.py writes or the reference's own (`state_dict` + `config`, DistributedDataParallel's "module." prefix removed).
 Writes audio_<n><suffix>.wav (16-bit PCM, each utterance scaled to full range as the reference does) and DLLogger records
 (waveglow_latency, waveglow_items_per_sec, denoiser_latency, latency).
@@ -25,10 +25,10 @@ from .model import DEFAULT_CONFIG, WaveGlow
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="WaveGlow inference on MI355X (mel spectrogram to audio)", allow_abbrev=False)
-    p.add_argument("-i", "--input", type=str, default=None, help="input text: needs Tacotron2 inference, which is not built")
+    p.add_argument("-i", "--input", type=str, default=None, help="input text: see deeplearningexamples_amd.tacotron2.inference")
     p.add_argument("-o", "--output", required=True, help="output folder to save audio (file per utterance)")
     p.add_argument("--suffix", type=str, default="", help="output filename suffix")
-    p.add_argument("--tacotron2", type=str, default=None, help="Tacotron2 checkpoint: its inference is not built")
+    p.add_argument("--tacotron2", type=str, default=None, help="Tacotron2 checkpoint: see deeplearningexamples_amd.tacotron2.inference")
     p.add_argument("--waveglow", type=str, default=None, help="full path to the WaveGlow model checkpoint file")
     p.add_argument("-s", "--sigma-infer", default=0.9, type=float)
     p.add_argument("-d", "--denoising-strength", default=0.01, type=float, help="0 skips the denoiser")
@@ -55,8 +55,8 @@ def parse_args(argv=None):
 
 def _reject_unbuilt(args):
     if args.input is not None or args.tacotron2 is not None:
-        raise SystemExit("-i / --tacotron2: text to mel (Tacotron2's autoregressive inference) is not built; "
-                         "pass a spectrogram with --mel FILE.pt or --synth-data")
+        raise SystemExit("-i / --tacotron2: text to speech (Tacotron2 + WaveGlow) is python -m deeplearningexamples_amd.tacotron2.inference; "
+                         "this entry point takes a spectrogram: --mel FILE.pt or --synth-data")
     if args.cpu:
         raise SystemExit("--cpu: this path runs on the MI355X only")
     if args.fp16 and args.amp_dtype != "fp16":

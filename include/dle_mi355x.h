@@ -731,6 +731,32 @@ int dle_t2_mel_loss(const float* out_all, int64_t ld_out, const void* post, cons
 int dle_t2_mask_rows(void* x, int64_t ld, int cols, const int64_t* lengths, int64_t B, int To, float value, int dtype,
                      hipStream_t stream);
 
+/* ---- Tacotron2 inference (csrc/tacotron2.hip): the free-running decoder step of Decoder.infer (model.py:515-595) -------------
+ * RNG contract of the prenet's dropout, which stays on at inference (model.py:129): the keep mask of decoder step t (0-based),
+ * prenet layer l (0 or 1), over the row-major [B, prenet_dim] block is the counter-based stream of csrc/dropout.h with
+ * (seed, call offset 1 + 2 t + l), p = 0.5 (kept values x 2).  t is read from a DEVICE word, so a captured graph draws fresh
+ * masks on every replay and the same seed gives the same spectrogram.
+ * state: int64 [4] on the device.  [0] / [1] = the step index as read by even / odd steps: a launch of parity p reads state[p],
+ * dle_t2_frame_infer writes state[1 - p] = t + 1 (no launch reads a word that a workgroup of the same launch writes);
+ * [2] = n_steps, the number of steps up to and including the first one after which no sample is unfinished (max_steps if that
+ * never happens); [3] = 1 once that step has run.  Reset all four to 0 before step 0.
+ * dle_t2_prenet_infer: relu(x W0^T) -> dropout -> relu(. W1^T) -> dropout for B <= 8 rows.  frame fp32 [B, NM] (NULL: the go
+ *   frame, zeros), rounded to 16 bits as the trainer's decoder input is; w0 [P, NM], w1 [P, P] 16-bit; dst 16-bit [B, P] rows of
+ *   pitch ld_dst (the prenet columns of the attention LSTM's operand); mask0 / mask1 (optional): the bit-packed keep masks
+ *   [B P / 8] of the two layers; step_dev = &state[t & 1].
+ * dle_t2_frame_infer: the tail of step t = state[parity].  hc 16-bit [B, K] = [decoder_hidden | context]; w 16-bit [NM + 1, K] =
+ *   linear_projection's rows then gate_layer's, bias fp32 [NM + 1]; mel_out fp32 [B, out_steps, NM] and gate_out fp32
+ *   [B, out_steps] receive row t; frame_next fp32 [B, NM] the next step's prenet input; then model.py:578-582 on the device:
+ *   dec = sigmoid(gate) <= gate_threshold; not_finished *= dec; mel_lengths += not_finished (int32 [B]); n_steps / done / the step
+ *   words as above.  A step with t >= max_steps (or out_steps) only advances the step words.  w0 != NULL: ONE workgroup runs the
+ *   frame and, behind it, the prenet of step t + 1 into pre_dst (pitch ld_pre) -- the one-launch form of the pair. */
+int dle_t2_prenet_infer(const float* frame, const void* w0, const void* w1, void* dst, int64_t ld_dst, void* mask0, void* mask1,
+                        uint64_t seed, const int64_t* step_dev, int B, int NM, int P, int dtype, hipStream_t stream);
+int dle_t2_frame_infer(const void* hc, int64_t ld_hc, const void* w, int64_t ldw, const float* bias, float* mel_out,
+                       float* gate_out, float* frame_next, int32_t* not_finished, int32_t* mel_lengths, int64_t* state, int parity,
+                       float gate_threshold, int max_steps, int64_t out_steps, const void* w0, const void* w1, void* pre_dst,
+                       int64_t ld_pre, uint64_t seed, int B, int NM, int K, int P, int dtype, hipStream_t stream);
+
 /* ---- the ReLU of an MLP layer as one bit per element (csrc/gemm8_kernel.h, round 6; Recommendation/DLRM/dlrm/nn/mlps.py:38-43,
  * 106-114 = apex mlp_cuda forward / backward).  dle_gemm8_relu_bits_try: Y [M, N] = relu(X [M, K] W [N, K]^T + bias) AND the keep
  * bits of Y (bits [M N / 8]: bit (m N + n) & 7 of byte (m N + n) >> 3 = rounded Y > 0); dense Y, N % 16 == 0.
