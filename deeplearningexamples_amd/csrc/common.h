@@ -3,13 +3,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <atomic>
 #include <mutex>
+// the published C ABI: dtype and epilogue codes, and the prototype every extern "C" definition is compiled against
+#include "../../include/dle_mi355x.h"
 
 #define DLE_WAVE 64
-
-// dtype codes of the C ABI (include/dle_mi355x.h)
-enum { DLE_F32 = 0, DLE_F16 = 1, DLE_BF16 = 2 };
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8_t;
 typedef __attribute__((ext_vector_type(4))) _Float16 half4_t;
@@ -32,6 +32,20 @@ extern "C" void dle_set_error(const char* fmt, ...);
     }                                       \
   } while (0)
 
+// The `*_try` convention.  A kernel entry whose name ends in `_try` (and dle_emb_onehot_partials) answers
+//     0 = declined, nothing launched (the caller goes on to its next kernel);
+//     1 = launched;
+//     anything else = error, handed up unchanged (-1: DLE_CHECK_ARG; a hipError_t is reported as e + 1000 so that it never
+//     reads as 0 or 1; the message is in dle_last_error()).
+// DLE_TRY(call, on_launched): the one call-site idiom -- run `on_launched` (a return, or the bookkeeping of that route) when
+// the kernel took the launch, hand an error up, fall through when it declined.
+#define DLE_TRY(call, on_launched)            \
+  do {                                        \
+    const int try_rc__ = (call);              \
+    if (try_rc__ == 1) { on_launched; }       \
+    else if (try_rc__ != 0) return try_rc__;  \
+  } while (0)
+
 #define DLE_LAUNCH_CHECK()                                        \
   do {                                                            \
     hipError_t e__ = hipGetLastError();                           \
@@ -40,6 +54,13 @@ extern "C" void dle_set_error(const char* fmt, ...);
       return (int)e__;                                            \
     }                                                             \
   } while (0)
+
+// A DLE_* environment switch as an integer, `def` when unset.  The only reader of the environment (rccl_comm.hip aside);
+// DESIGN.md section 0 lists every name.  Call sites cache the value in a function-local static unless they say "per call".
+inline int dle_env_int(const char* name, int def) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : def;
+}
 
 // ---- per-device host state (inline: one instance of each static across the library) ------------------------------
 #define DLE_MAX_DEVICES 64

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* 
   }
 }
 
-static int g_w3_mode = -1;               // -1 / 1: on where it applies, 0: off (A/B harnesses, DLE_CONV3X3_WGRAD=0)
+static int g_w3_mode = -1;               // 0: off (A/B harnesses); anything else: on where it applies
 extern "C" int dle_conv3x3_wgrad_mode(int mode) {
   const int old = g_w3_mode;
   g_w3_mode = mode;
@@ -254,11 +254,10 @@ extern "C" int dle_conv3x3_wgrad_mode(int mode) {
 // Workspace the halo-tile weight gradient needs (one 64 x 9 x 64 fp32 block per workgroup, 256 workgroups).
 extern "C" int64_t dle_conv3x3_wgrad_workspace(void) { return 256LL * 64 * 9 * 64 * 4; }
 
-// 1: launched; 0: outside the envelope (the caller uses the split-K implicit GEMM); > 1: error.
+// 0: outside the envelope (the caller uses the split-K implicit GEMM).
 extern "C" int dle_conv3x3_wgrad_try(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int dtype,
                                      int accumulate, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  static const int env_mode = getenv("DLE_CONV3X3_WGRAD") ? atoi(getenv("DLE_CONV3X3_WGRAD")) : -1;
-  if (g_w3_mode == 0 || (g_w3_mode < 0 && env_mode == 0)) return 0;
+  if (g_w3_mode == 0) return 0;
   if ((C & 63) || (Ko & 63) || (dtype != DLE_F16 && dtype != DLE_BF16)) return 0;
   if (((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dw) | ((uintptr_t)workspace)) & 15) != 0) return 0;
   const int nsub = (Ko / 64) * (C / 64);

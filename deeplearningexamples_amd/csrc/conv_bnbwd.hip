@@ -403,16 +403,14 @@ extern "C" int64_t dle_conv1x1_bnbwd_wgrad_workspace(int M, int bnred) {
   return (int64_t)bnb_wgrad_groups(M) * 256 * 64 * 4 + (bnred ? (int64_t)((M + 63) / 64) * 4 * 128 * 4 : 0);
 }
 
-hipError_t wgrad1x1_fold(const float* ws, float* dw, long long total4, int G, int accumulate, hipStream_t stream);   // wgrad1x1.hip
-
 // x / gw / workspace NULL: the plain form (dt written); else the weight-gradient form (dt unused, gw [K][N] fp32 written)
 static int bnb_launch(const void* dy, const void* t, const void* relu_mask, const void* w, void* dt, void* dx, const float* mean,
                       const float* rstd, const float* gamma, const float* dgamma, const float* dbeta, const void* t2,
                       const void* bits2, const float* mean2, const float* rstd2, float* partial, int64_t partial_bytes,
                       const void* x, float* gw, void* workspace, int64_t workspace_bytes, int M, int N, int K, int dtype,
                       hipStream_t stream) {
-  static const char* pin = getenv("DLE_CONV_BNBWD");
-  if (pin && atoi(pin) == 0) return 0;
+  static const int on = dle_env_int("DLE_CONV_BNBWD", 1);
+  if (!on) return 0;
   const bool wg = x != nullptr;
   if (dtype != DLE_F16 && dtype != DLE_BF16) return 0;
   if (M < 4096 || K != 256 || N != 64) return 0;

@@ -237,7 +237,7 @@ static int bl_nw(int K, int N) { return (K > 128 && bl_tn(N) == 128) ? 8 : 4; }
 // is 133 KiB -- ONE 8-wave workgroup per CU, 16 k steps of fragments per lane (64 + 64 registers with the residual).  Measured
 // at batch 256 (200704 x 128 x 512 + residual): 172 us fused against 117 + 52 us apart -- no gain at two wavefronts per SIMD, so
 // the two-launch sequence stays the default; DLE_CONV_BNLOAD_K512=1 (read per call) lets the fused form through (tests, A/B runs)
-static int bl_k512() { const char* e = getenv("DLE_CONV_BNLOAD_K512"); return e ? atoi(e) : 0; }
+static int bl_k512() { return dle_env_int("DLE_CONV_BNLOAD_K512", 0); }
 
 // Number of statistics rows dle_conv1x1_bnload_fwd writes for (M, N, K); 0: the shape is outside the kernel's envelope.
 extern "C" int dle_conv1x1_bnload_groups(int M, int N, int K) {
@@ -260,8 +260,6 @@ static int bnload_launch(const void* t, const void* res, const void* w, void* ou
                          const float* rstd, const float* gamma, const float* beta, const float* mean_r, const float* rstd_r,
                          const float* gamma_r, const float* beta_r, float* stats, int64_t stats_bytes,
                          int M, int N, int K, int dtype, hipStream_t stream) {
-  static const char* pin = getenv("DLE_CONV_BNLOAD");
-  if (pin && atoi(pin) == 0) return 0;
   if (dtype != DLE_F16 && dtype != DLE_BF16) return 0;
   const int groups = dle_conv1x1_bnload_groups(M, N, K);
   if (groups == 0 || !t || !w || !out || !y || !bits || !mean || !rstd || !gamma || !beta) return 0;

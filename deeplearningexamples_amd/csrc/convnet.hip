@@ -1375,8 +1375,7 @@ extern "C" int dle_maxpool_bwd(const void* dy, const void* argmax, void* dx, int
   DLE_CHECK_ARG(dy && dx && argmax, "maxpool_bwd: null pointer");
   const int P = (H + 2 * pad - ksize) / stride + 1, Q = (W + 2 * pad - ksize) / stride + 1;
   const int grid = cn_grid((long long)N * H * W * (C / 8), 256, 8192);
-  static const int patch_mode = getenv("DLE_MAXPOOL_BWD_PATCH") ? atoi(getenv("DLE_MAXPOOL_BWD_PATCH")) : 1;
-  if (patch_mode && ksize == 3 && stride == 2 && pad == 1 && (H & 1) == 0 && (W & 1) == 0 && (long long)N * H * W * (C / 8) < 0x7FFFFFFFLL) {
+  if (ksize == 3 && stride == 2 && pad == 1 && (H & 1) == 0 && (W & 1) == 0 && (long long)N * H * W * (C / 8) < 0x7FFFFFFFLL) {
     const int gp = cn_grid((long long)N * P * Q * (C / 8), 256, 8192);
     if (dtype == DLE_F16) hipLaunchKernelGGL(maxpool_bwd_k3s2_patch_kernel<DLE_F16>, dim3(gp), dim3(256), 0, stream, (const unsigned short*)dy, (const unsigned char*)argmax, (unsigned short*)dx, N, H, W, C / 8, P, Q);
     else hipLaunchKernelGGL(maxpool_bwd_k3s2_patch_kernel<DLE_BF16>, dim3(gp), dim3(256), 0, stream, (const unsigned short*)dy, (const unsigned char*)argmax, (unsigned short*)dx, N, H, W, C / 8, P, Q);

@@ -404,9 +404,8 @@ extern "C" int dle_dot_interact_fwd(const void* x, void* out, int batch, int row
     DLE_CHECK_ARG(lds <= 64 * 1024, "dot_interact_fwd: row too wide for LDS (%d)", OW);
     dim3 grid((batch + 3) / 4), block(256);
     // persistent walk with register prefetch for the widths of the metric (C = 128) and its neighbours
-    static const int walk = getenv("DLE_DOT_FWD_WALK") ? atoi(getenv("DLE_DOT_FWD_WALK")) : 1;
-    static const int per_cu = getenv("DLE_DOT_FWD_WG_PER_CU") ? atoi(getenv("DLE_DOT_FWD_WG_PER_CU")) : 2;     // (65536 x 27 x 128: 92 us at 2, 97 at 3, 103 at 4-8; one-shot form 125)
-    if (walk && (cols == 64 || cols == 128) && batch >= 4096) {
+    const int per_cu = 2;     // workgroups per CU (65536 x 27 x 128: 92 us at 2, 97 at 3, 103 at 4-8; one-shot form 125)
+    if ((cols == 64 || cols == 128) && batch >= 4096) {
       dim3 wgrid((unsigned)(grid.x < 256u * per_cu ? grid.x : 256u * per_cu));
 #define GOW(DT, NK) hipLaunchKernelGGL((dot_fwd_mfma_walk<DT, NK>), wgrid, block, lds, stream, (const unsigned short*)x, \
                                        (unsigned short*)out, batch, rows, OW)
@@ -434,8 +433,6 @@ extern "C" int dle_dot_interact_fwd(const void* x, void* out, int batch, int row
   return 0;
 }
 
-extern "C" int dle_check_nonfinite(const void* x, float* found_inf, int64_t n, int dtype, hipStream_t stream);
-
 extern "C" int dle_dot_interact_bwd_checked(const void* x, const void* upstream, void* grad, void* mlp_grad,
                                             int batch, int rows, int cols, int dtype, int force_generic,
                                             float* found_inf, hipStream_t stream) {
@@ -449,7 +446,7 @@ extern "C" int dle_dot_interact_bwd_checked(const void* x, const void* upstream,
   if (fast) {
     const size_t lds = (size_t)4 * (32 * (cols + 8) + 32 * DOT_BWD_USTRIDE + 256) * 2;
     // persistent: two workgroups per CU (180 registers at C = 128), each wavefront walks its samples
-    static const int per_cu = getenv("DLE_DOT_BWD_WG_PER_CU") ? atoi(getenv("DLE_DOT_BWD_WG_PER_CU")) : 2;
+    const int per_cu = 2;
     int nblk = (batch + 3) / 4;
     if (nblk > 256 * per_cu) nblk = 256 * per_cu;
     dim3 grid(nblk), block(256);

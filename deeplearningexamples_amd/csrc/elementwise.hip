@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const unsigned short* __re
 
 extern "C" int dle_act_bwd(const void* g, const void* src, void* out, int64_t n, int act, int dtype, hipStream_t stream) {
   DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "act_bwd: 16-bit dtypes only");
-  DLE_CHECK_ARG(act == 5 || act == 7, "act_bwd: act must be DLE_ACT_GELU_BWD or DLE_ACT_TANH_BWD");
+  DLE_CHECK_ARG(act == DLE_ACT_GELU_BWD || act == DLE_ACT_TANH_BWD, "act_bwd: act must be DLE_ACT_GELU_BWD or DLE_ACT_TANH_BWD");
   DLE_CHECK_ARG(n >= 0 && n % 8 == 0, "act_bwd: element count must be a multiple of 8");
   if (n == 0) return 0;
   DLE_CHECK_ARG(g && src && out, "act_bwd: null pointer");

@@ -340,12 +340,6 @@ __global__ __launch_bounds__(256) void emb_adam_mid_fold(EaTable tb, const int* 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-extern "C" int dle_emb_onehot_partials(const int64_t* rows, const void* grad, const float* skip_flag_dev, const int* tab_t,
-                                       const int64_t* tab_base, const int* tab_rows, int n_tab, int64_t batch, int tables, int dim,
-                                       int64_t grad_batch_stride, int grad_dtype, void* ws, int64_t ws_bytes, int* slices_out,
-                                       hipStream_t stream);
-extern "C" int64_t dle_emb_onehot_workspace_bytes(int n_tables, int64_t batch);
-
 static long long ea_align(long long v) { return (v + 255) / 256 * 256; }
 
 // Scratch layout: [one-hot partials of the small tables (dim 128) | LDS-form partials of every small table | touched bytes |
@@ -459,17 +453,18 @@ extern "C" int dle_emb_adam_dedup_ws(float* weight, float* exp_avg, float* exp_a
     hipLaunchKernelGGL(emb_adam_mark, dim3(ea_grid((long long)batch * sm.n, 256)), dim3(256), 0, stream, (const long long*)rows,
                        (unsigned char*)(wsb + pl.touched_off), sm, (long long)batch, tables, skip_flag_dev);
     DLE_LAUNCH_CHECK();
-    int oh_slices = 0, rc = 0;
+    int oh_slices = 0;
+    bool onehot = false;
     if (dim == 128 && grad_dtype != DLE_F32) {
       static_assert(sizeof(long long) == sizeof(int64_t), "table bases are passed as int64");
-      rc = dle_emb_onehot_partials(rows, grad, skip_flag_dev, sm.t, (const int64_t*)sm.base, sm.rows, sm.n, batch, tables, dim,
-                                   grad_batch_stride, grad_dtype, wsb + pl.oh_off, pl.lds_off - pl.oh_off, &oh_slices, stream);
-      if (rc > 1) return rc;
+      DLE_TRY(dle_emb_onehot_partials(rows, grad, skip_flag_dev, sm.t, (const int64_t*)sm.base, sm.rows, sm.n, batch, tables, dim,
+                                      grad_batch_stride, grad_dtype, wsb + pl.oh_off, pl.lds_off - pl.oh_off, &oh_slices, stream),
+              onehot = true);
     }
     int n_lds = 0, max_rows = 0;
     long long lds_pos = pl.lds_off / 4;
     for (int k = 0; k < sm.n; ++k) {
-      if (rc == 1) {                                  // the one-hot kernel's layout: [k][slice][128 rows][128]
+      if (onehot) {                                   // the one-hot kernel's layout: [k][slice][128 rows][128]
         sm.slices[k] = oh_slices;
         sm.pbase[k] = (pl.oh_off / 4) + (long long)k * oh_slices * 128 * 128;
         sm.sstride[k] = 128 * 128;

@@ -248,14 +248,13 @@ extern "C" int dle_emb_onehot_try(float* weight, const int64_t* rows, const void
                                   const float* scale_dev, const float* skip_flag_dev, const int* tab_t, const int64_t* tab_base,
                                   const int* tab_rows, int n_tab, int64_t batch, int tables, int dim, int64_t grad_batch_stride,
                                   int grad_dtype, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  static const int mode = getenv("DLE_EMB_ONEHOT") ? atoi(getenv("DLE_EMB_ONEHOT")) : 1;
-  if (!mode || n_tab <= 0 || n_tab > 64 || dim != OH_D || !ws) return 0;
+  if (n_tab <= 0 || n_tab > 64 || dim != OH_D || !ws) return 0;
   // NON-FINITE GRADIENTS: dW = OneHot^T G multiplies EVERY gradient row into every row of the tiny table (by 0 or 1), so one
   // inf / NaN gradient row poisons the whole table (0 * inf = NaN), where the register / LDS forms and the reference's atomicAdd
   // only touch the row that was looked up.  The fp16 path is protected by ordering: the GradScaler's found_inf is final BEFORE
   // this launch (dle_check_nonfinite runs on the gradient first) and arrives here as skip_flag_dev, which drops the whole step.
   // A caller without a scaler (bf16, skip_flag_dev == NULL) gets a poisoned table instead of a poisoned row from a non-finite
-  // gradient -- the run is lost either way; DLE_EMB_ONEHOT=0 keeps the row-local forms.
+  // gradient -- the run is lost either way.
   OhArgs p;
   if (!oh_envelope(p, weight, rows, grad, lr_dev, lr_host, scale_dev, skip_flag_dev, tab_t, tab_base, tab_rows, n_tab, batch, tables,
                    grad_batch_stride, grad_dtype, ws, ws_bytes))

@@ -620,7 +620,7 @@ __global__ __launch_bounds__(256) void emb_sgd_lists(float* __restrict__ weight,
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (!ok[u] || h[u] != iu[u]) continue;        // small-table lookup / not the list head: the head does the work
-      if (!SPEC) wv[u] = ((const float4_t*)(weight + r[u] * (long long)(D4 * 4)))[lc];     // (DLE_EMB_SPEC=0: heads only, depth 3)
+      if (!SPEC) wv[u] = ((const float4_t*)(weight + r[u] * (long long)(D4 * 4)))[lc];     // (heads only, depth 3; not instantiated: SPEC = true measured faster)
       float4_t sacc = In4<IDT>::up(g[u]);
       int j = nx[u];
       while (j >= 0) {
@@ -722,13 +722,6 @@ extern "C" int dle_emb_small_table_mask(const int64_t* table_offsets_host, int t
   return 0;
 }
 
-extern "C" int dle_emb_onehot_try(float* weight, const int64_t* rows, const void* grad, const float* lr_dev, float lr_host,
-                                  const float* scale_dev, const float* skip_flag_dev, const int* tab_t, const int64_t* tab_base,
-                                  const int* tab_rows, int n_tab, int64_t batch, int tables, int dim, int64_t grad_batch_stride,
-                                  int grad_dtype, void* ws, int64_t ws_bytes, hipStream_t stream);
-
-extern "C" int64_t dle_emb_onehot_workspace_bytes(int n_tables, int64_t batch);
-
 // Scratch layout of dle_emb_sgd_dedup_ws for 16-bit gradients: [one-hot partial blocks of the tiny tables | sub-list heads of the mid
 // tables | their partial sums], each part 256-byte aligned.
 struct EmbScratchPlan {
@@ -737,14 +730,13 @@ struct EmbScratchPlan {
 };
 static EmbScratchPlan emb_scratch_plan(const int64_t* table_offsets_host, int tables, int dim, int64_t batch) {
   EmbScratchPlan pl = {};
-  static const int mid_mode = getenv("DLE_EMB_MID") ? atoi(getenv("DLE_EMB_MID")) : 1;
   int n_small = 0;
   for (int t = 0; t < tables; ++t) {
     const long long r = table_offsets_host[t + 1] - table_offsets_host[t];
     if (r * dim * 4 <= DLE_EMB_SMALL_LDS_BYTES && n_small < 64) {
       ++n_small;
       if (r <= 128 && dim <= 128 && (dim & 1) == 0) ++pl.n_tiny;
-    } else if (mid_mode && r <= EMB_MID_ROWS && dim <= 128 && tables <= 128 && pl.n_mid < EMB_MID_TABLES) {
+    } else if (r <= EMB_MID_ROWS && dim <= 128 && tables <= 128 && pl.n_mid < EMB_MID_TABLES) {
       ++pl.n_mid;
       pl.mid_rows += (int)r;
     }
@@ -794,9 +786,8 @@ extern "C" int dle_emb_sgd_dedup_ws(float* weight, const int64_t* rows, const vo
   SmallTables tiny, lds_t;
   tiny.n = 0; lds_t.n = 0;
   int max_rows = 0, max_rows_tiny = 0;
-  static const int tiny_mode = getenv("DLE_EMB_TINY") ? atoi(getenv("DLE_EMB_TINY")) : 1;
   for (int i = 0; i < st.n; ++i) {
-    const bool is_tiny = tiny_mode && grad_dtype != DLE_F32 && st.rows[i] <= 128 && dim <= 128 && (dim & 1) == 0 &&
+    const bool is_tiny = grad_dtype != DLE_F32 && st.rows[i] <= 128 && dim <= 128 && (dim & 1) == 0 &&
                          (grad_batch_stride & 1) == 0;        // (fp32 gradients: the LDS form -- not the train step's path)
     SmallTables& dst = is_tiny ? tiny : lds_t;
     dst.t[dst.n] = st.t[i]; dst.base[dst.n] = st.base[i]; dst.rows[dst.n] = st.rows[i];
@@ -809,11 +800,9 @@ extern "C" int dle_emb_sgd_dedup_ws(float* weight, const int64_t* rows, const vo
   const bool ws_ok = plan_ok && ws_bytes >= pl.total;
   if (tiny.n > 0 && ws_ok && pl.onehot_bytes > 0 && tiny.n == pl.n_tiny) {
     static_assert(sizeof(long long) == sizeof(int64_t), "table bases are passed as int64");
-    const int rc = dle_emb_onehot_try(weight, rows, grad, lr_dev, lr_host, scale_dev, skip_flag_dev, tiny.t,
-                                      (const int64_t*)tiny.base, tiny.rows, tiny.n, batch, tables, dim, grad_batch_stride,
-                                      grad_dtype, ws, pl.onehot_bytes, stream);
-    if (rc > 1) return rc;
-    if (rc == 1) tiny.n = 0;
+    DLE_TRY(dle_emb_onehot_try(weight, rows, grad, lr_dev, lr_host, scale_dev, skip_flag_dev, tiny.t, (const int64_t*)tiny.base,
+                               tiny.rows, tiny.n, batch, tables, dim, grad_batch_stride, grad_dtype, ws, pl.onehot_bytes, stream),
+            tiny.n = 0);
   }
   if (tiny.n > 0) {
     // one 16-wavefront workgroup per CU and table slice; >= 2048 samples per workgroup
@@ -890,9 +879,7 @@ extern "C" int dle_emb_sgd_dedup_ws(float* weight, const int64_t* rows, const vo
                        is_small_dev, skip_flag_dev, (int)n_lk, map, mid);
     DLE_LAUNCH_CHECK();
     const int grid = grid_for(n_lk, 4 * 4);
-    static const int spec = getenv("DLE_EMB_SPEC") ? atoi(getenv("DLE_EMB_SPEC")) : 1;
-#define GO(IDT, VT) do { if (spec) hipLaunchKernelGGL((emb_sgd_lists<IDT, true>), dim3(grid), dim3(256), 0, stream, weight, (const long long*)rows, (const VT*)grad, head, (const int*)next, is_small_dev, lr_dev, lr_host, scale_dev, skip_flag_dev, (int)n_lk, map, D4, gs4, mid); \
-    else hipLaunchKernelGGL((emb_sgd_lists<IDT, false>), dim3(grid), dim3(256), 0, stream, weight, (const long long*)rows, (const VT*)grad, head, (const int*)next, is_small_dev, lr_dev, lr_host, scale_dev, skip_flag_dev, (int)n_lk, map, D4, gs4, mid); } while (0)
+#define GO(IDT, VT) hipLaunchKernelGGL((emb_sgd_lists<IDT, true>), dim3(grid), dim3(256), 0, stream, weight, (const long long*)rows, (const VT*)grad, head, (const int*)next, is_small_dev, lr_dev, lr_host, scale_dev, skip_flag_dev, (int)n_lk, map, D4, gs4, mid)
     if (grad_dtype == DLE_F32) GO(DLE_F32, float4_t);
     else if (grad_dtype == DLE_F16) GO(DLE_F16, ushort4_t);
     else GO(DLE_BF16, ushort4_t);

@@ -26,15 +26,9 @@
 //    (8 B / 16 B stores); bias, ReLU, tanh-GELU (+ pre-activation side output), ReLU-backward
 //    masking, fp32 accumulation and split-K (fp32 atomics) are fused in the epilogue.
 //  * workgroup ids are remapped so the 8 XCDs each walk a contiguous band of tiles (private L2s).
-#include "common.h"
-#include <stdlib.h>
+#include "gemm_family.h"
 
-#define BM 128
-#define BN 128
-#define BK 64
 #define SLAB_MODE(p) false
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_BWD = 3 };
 
 struct GemmArgs {
   const unsigned short* A;
@@ -124,12 +118,6 @@ __device__ __forceinline__ void swrite_tr(const ushort8_t (&r)[4], unsigned shor
     ushort4_t w = {r[0][j], r[1][j], r[2][j], r[3][j]};
     *(ushort4_t*)(tile + row * BK + ((((kg >> 1) ^ swz(row))) << 3) + ((kg & 1) << 2)) = w;
   }
-}
-
-__device__ __forceinline__ float gelu_tanh(float x) {
-  const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float u = k0 * (x + k1 * x * x * x);
-  return 0.5f * x * (1.0f + fast_tanh(u));
 }
 
 template <int DT, bool A_KC, bool B_KC>
@@ -483,100 +471,11 @@ extern "C" int dle_colsum_batched(const int64_t* table_dev, int n, int64_t M, in
   return 0;
 }
 
-extern "C" int dle_gemm_dma_try(const void* A, const void* B, void* C, void* aux, const float* bias,
-                                const void* mask_src, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-                                int a_kc, int b_kc, int in_dtype, int out_dtype, int act, int splitk,
-                                int accumulate, float alpha, void* workspace, int64_t workspace_bytes,
-                                hipStream_t stream);
-
-extern "C" int dle_gemm8_try(const void* A, const void* B, void* C, void* aux, const float* bias, const void* src, int M, int N,
-                             int K, int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc, int in_dtype, int out_dtype,
-                             int act, int splitk, int accumulate, float alpha, float* ws, float* stats, hipStream_t stream);   // gemm8.hip
-
-extern "C" int dle_gemm_smallm_try(const void* A, const void* B, void* C, const float* bias, const void* src, int M, int N, int K,
-                                   int64_t lda, int64_t ldb, int64_t ldc, int in_dtype, int out_dtype, int act_add, int accumulate,
-                                   float alpha, hipStream_t stream);     // gemm_smallm.hip
-
-extern "C" int dle_gemm_expand_try(const void* A, const void* B, void* C, const void* src, const void* bits, float* stats, int M,
-                                   int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_kc, int in_dtype, int out_dtype,
-                                   int act, hipStream_t stream);           // gemm_expand.hip
-
-// C ABI.  a_kc / b_kc: operand stored with the contraction dimension contiguous (see header).
-extern "C" int dle_gemm(const void* A, const void* B, void* C, void* aux, const float* bias,
-                        const void* mask_src, int M, int N, int K, int64_t lda, int64_t ldb,
-                        int64_t ldc, int a_kc, int b_kc, int in_dtype, int out_dtype, int act,
-                        int splitk, int accumulate, float alpha, void* workspace, int64_t workspace_bytes,
-                        hipStream_t stream) {
-  DLE_CHECK_ARG(A && B && C, "gemm: null pointer");
-  DLE_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "gemm: negative dimension");
-  DLE_CHECK_ARG(in_dtype == DLE_F16 || in_dtype == DLE_BF16, "gemm: inputs must be f16/bf16 (got %d)", in_dtype);
-  DLE_CHECK_ARG(out_dtype == DLE_F32 || out_dtype == DLE_F16 || out_dtype == DLE_BF16, "gemm: bad out dtype");
-  DLE_CHECK_ARG(!(a_kc == 0 && b_kc != 0), "gemm: (A m-contiguous, B k-contiguous) is not a hot-path layout");
-  const bool needs_src = act == ACT_RELU_BWD || act == 4 || act == 5 || act == 7 || act == 8 || act == 9;   // RELU_BWD, ADD, GELU_BWD, TANH_BWD, ADD_MASKED, MUL
-  DLE_CHECK_ARG(act >= 0 && act <= 10, "gemm: unknown epilogue %d", act);
-  DLE_CHECK_ARG(!needs_src || mask_src, "gemm: this epilogue needs mask_src");
-  DLE_CHECK_ARG(act != 8 || (aux && (ldc & 7) == 0), "gemm: the masked add reads its keep bits through aux (ldc a multiple of 8)");
-  DLE_CHECK_ARG(act != 10 || aux, "gemm: DLE_ACT_GELU_DAUX writes the derivative to aux");
-  DLE_CHECK_ARG(!needs_src || out_dtype == in_dtype, "gemm: mask_src dtype = in dtype = out dtype");
-  if (splitk < 1) splitk = 1;
-  {
-    const int kt = K > 0 ? (K + BK - 1) / BK : 1;
-    if (splitk > kt) splitk = kt;          // every K slice owns at least one K tile
-  }
-  if (splitk > 1)
-    DLE_CHECK_ARG(out_dtype == DLE_F32 && !bias && act == ACT_NONE && !aux, "gemm: split-K needs a plain fp32 output");
-  else
-    DLE_CHECK_ARG(!accumulate || out_dtype == DLE_F32, "gemm: accumulate needs fp32 output");
-  if (M == 0 || N == 0) return 0;
-  {
-    // fast path: LDS-DMA fed kernel (gemm_dma.hip); DLE_GEMM_LEGACY=1 pins the register-staged kernel
-    static const bool legacy = getenv("DLE_GEMM_LEGACY") != nullptr && getenv("DLE_GEMM_LEGACY")[0] == '1';
-    // few rows (recurrent steps, heads): the weight-streaming kernel of gemm_smallm.hip -- N / 16..32 workgroups instead of a
-    // dozen 128x128 tiles
-    if (!legacy && K > 0 && M <= 256 && a_kc && b_kc && splitk == 1 && !aux && (act == ACT_NONE || act == 4) &&
-        (!accumulate || out_dtype == DLE_F32)) {
-      const int r = dle_gemm_smallm_try(A, B, C, bias, mask_src, M, N, K, lda, ldb, ldc, in_dtype, out_dtype, act == 4, accumulate,
-                                        alpha, stream);
-      if (r == 1) return 0;
-      if (r != 0) return r;
-    }
-    // the masked-addend data gradient of the deepest stage's conv1 (K >= 512, M <= 65536 rows: 7 x 7 at batch 256): the
-    // ping-pong kernel's source-tensor epilogue with the keep bits (gemm8_kernel.h, ACT_ADD_MASKED); DLE_GEMM8_MASKED=0 keeps the
-    // streaming kernel below
-    // (K >= 512 only: at K = 256 -- 50176 x 1024 x 256, four K tiles per item -- the item is all epilogue and the streaming kernel
-    //  below is faster, 63 against 71 us; at K = 512 the ping-pong kernel wins, 57 against 63 us: profiles/r06_rn50_shapes_*.txt)
-    if (!legacy && act == 8 && a_kc && !b_kc && splitk == 1 && !accumulate && !bias && alpha == 1.0f && K >= 512) {
-      static const int on = getenv("DLE_GEMM8_MASKED") ? atoi(getenv("DLE_GEMM8_MASKED")) : 1;
-      static const long long maxm = getenv("DLE_GEMM8_MASKED_MAXM") ? atoll(getenv("DLE_GEMM8_MASKED_MAXM")) : 65536;
-      if (on && M <= maxm) {
-        const int r = dle_gemm8_try(A, B, C, aux, bias, mask_src, M, N, K, lda, ldb, ldc, a_kc, b_kc, in_dtype, out_dtype, act, 1, 0,
-                                    alpha, nullptr, nullptr, stream);
-        if (r == 1) return 0;
-        if (r > 1) return r;
-      }
-    }
-    // many rows, K <= 256, N >= 2 K (the channel-widening 1x1 convolutions): the streaming kernel of gemm_expand.hip
-    // (store-only products with K = 64 stay on the tile kernel's PLAIN epilogue: 135 vs 152 us at 802816 x 256 x 64)
-    if (!legacy && a_kc && splitk == 1 && !accumulate && !bias && alpha == 1.0f &&
-        (act == ACT_NONE ? (!aux && K >= 128) : act == 4 ? !aux : act == 8)) {
-      const char* pin = getenv("DLE_GEMM_EXPAND");                          // probes / tests: "0" pins the tile kernels
-      if (!pin || atoi(pin) != 0) {
-        const int r = dle_gemm_expand_try(A, B, C, mask_src, act == 8 ? aux : nullptr, nullptr, M, N, K, lda, ldb, ldc, b_kc,
-                                          in_dtype, out_dtype, act == 0 ? 0 : act == 4 ? 1 : 2, stream);
-        if (r == 1) return 0;
-        if (r != 0) return r;
-      }
-    }
-    if (!legacy && K > 0) {
-      const int r = dle_gemm_dma_try(A, B, C, aux, bias, mask_src, M, N, K, lda, ldb, ldc, a_kc, b_kc, in_dtype,
-                                     out_dtype, act, splitk, accumulate, alpha, workspace, workspace_bytes, stream);
-      if (r == 1) return 0;
-      if (r != 0) return r;
-    }
-  }
-  DLE_CHECK_ARG(act <= ACT_RELU_BWD, "gemm: epilogue %d needs the aligned (LDS-DMA) path: K, lda, ldb multiples of 8, 16-byte "
-                "aligned operands", act);
-  if (splitk > 1 && !accumulate) {   // register-staged kernel: fp32 atomics into a cleared C
+// dle_gemm's last route (gemm_route.hip); prototype and contract in gemm_family.h
+int gemm_regs_launch(const void* A, const void* B, void* C, void* aux, const float* bias, const void* mask_src, int M, int N, int K,
+                     int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc, int in_dtype, int out_dtype, int act, int splitk,
+                     int accumulate, float alpha, hipStream_t stream) {
+  if (splitk > 1 && !accumulate) {   // fp32 atomics into a cleared C
     hipError_t e = ldc == N ? hipMemsetAsync(C, 0, (size_t)M * N * 4, stream)
                             : hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, (size_t)M, stream);
     if (e != hipSuccess) { dle_set_error("gemm memset: %s", hipGetErrorString(e)); return (int)e; }

@@ -4,7 +4,7 @@
 // ---- launcher ----------------------------------------------------------------------------------------------------------------
 static int g8_mode_value = -2;          // -2: read DLE_GEMM_8PH on first use; 0 off; 1 on
 extern "C" int dle_gemm8_mode(int mode) {
-  if (g8_mode_value == -2) g8_mode_value = getenv("DLE_GEMM_8PH") ? atoi(getenv("DLE_GEMM_8PH")) : 1;
+  if (g8_mode_value == -2) g8_mode_value = dle_env_int("DLE_GEMM_8PH", 1);
   const int prev = g8_mode_value;
   if (mode >= 0) g8_mode_value = mode;
   return prev;
@@ -12,7 +12,7 @@ extern "C" int dle_gemm8_mode(int mode) {
 
 static int g8_min_items_value = -1;     // -1: read DLE_GEMM_8PH_MIN_ITEMS on first use
 extern "C" int dle_gemm8_min_items(int n) {
-  if (g8_min_items_value < 0) g8_min_items_value = getenv("DLE_GEMM_8PH_MIN_ITEMS") ? atoi(getenv("DLE_GEMM_8PH_MIN_ITEMS")) : 128;
+  if (g8_min_items_value < 0) g8_min_items_value = dle_env_int("DLE_GEMM_8PH_MIN_ITEMS", 128);
   const int prev = g8_min_items_value;
   if (n >= 0) g8_min_items_value = n;
   return prev;
@@ -26,8 +26,6 @@ int g8_dbg_items = 0;
 #endif
 // instantiation units: gemm8.hip (store-only epilogues), gemm8_epi1.hip (bias / forward activations), gemm8_epi2.hip
 // (source-tensor epilogues); each returns 0 for a combination it does not carry
-extern "C" int g8_launch_epi1(const Gemm8Args* p, int dt, int am, int bm, int act, int grid, hipStream_t stream);
-extern "C" int g8_launch_epi2(const Gemm8Args* p, int dt, int am, int bm, int act, int grid, hipStream_t stream);
 static int g8_launch_epi0(const Gemm8Args* p, int dt, int am, int bm, int grid, hipStream_t stream) {
 #define G8_E0(DT) do { if (am == 0 && bm == 0) g8_launch<DT, 0, 0, 0, ACT_NONE>(*p, grid, stream); \
     else if (am == 0) g8_launch<DT, 0, 1, 0, ACT_NONE>(*p, grid, stream); else g8_launch<DT, 1, 1, 0, ACT_NONE>(*p, grid, stream); } while (0)
@@ -36,7 +34,7 @@ static int g8_launch_epi0(const Gemm8Args* p, int dt, int am, int bm, int grid, 
   return 1;
 }
 
-// 1: launched; 0: outside the envelope (the caller continues with the kernels of gemm_dma.hip); > 1: error.
+// The `*_try` convention of gemm_family.h; 0: outside the envelope (the caller continues with the kernels of gemm_dma.hip).
 // stats != NULL: column sums of the rounded output into stats[2 * ceil(M / 256)][N] (act = ReLU mask / stored derivative only).
 static int g8_try(const void* A, const void* B, void* C, void* aux, const float* bias, const void* src, int M, int N,
                   int K, int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc, int in_dtype, int out_dtype,
@@ -96,8 +94,6 @@ static int g8_try(const void* A, const void* B, void* C, void* aux, const float*
   } else return 0;
   // the three operand layouts of a linear layer, each with the epilogues its pass uses (the instantiation units decide)
   const int am = a_kc ? 0 : 1, bm = b_kc ? 0 : 1;
-  static const int tn_mode = getenv("DLE_GEMM_8PH_TN") ? atoi(getenv("DLE_GEMM_8PH_TN")) : 1;
-  if (am == 1 && !tn_mode) return 0;
   const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
   const long long nitems = tiles * splitk;
   const int min_items = dle_gemm8_min_items(-1);
@@ -112,8 +108,7 @@ static int g8_try(const void* A, const void* B, void* C, void* aux, const float*
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
   p.out_dtype = out_dtype; p.act = act; p.splitk = splitk; p.accumulate = accumulate; p.alpha = alpha;
-  static const int gm_env = getenv("DLE_GEMM_GM") ? atoi(getenv("DLE_GEMM_GM")) : 8;
-  p.gm = gm_env > 0 ? gm_env : 8;
+  p.gm = dle_gemm_gm();
   {
     const long long cb = splitk > 1 ? (long long)M * N * 4 : (long long)M * ldc * (out_dtype == DLE_F32 ? 4 : 2);
     p.c_bytes = cb < 0xFFFFFFFFLL ? (unsigned)cb : 0u;           // 0: the interior fast path is off (c_bytes == 0 below)
@@ -150,7 +145,7 @@ extern "C" int dle_gemm8_try(const void* A, const void* B, void* C, void* aux, c
 // C [M, N] = A [M, K] B [N, K]^T (16-bit, both k-contiguous) AND, per 128 output rows, the column sums and sums of squares of the
 // ROUNDED output: stats [M / 128][2][N] (row r = rows 128 r .. 128 r + 127) -- the 1x1 convolution forward with the batch
 // statistics of the BatchNorm behind it (dle_conv2d_fwd_colstats; fold with dle_bn_stats_from_partials, groups = M / 128).
-// M a multiple of 256.  1: launched; 0: outside the envelope; > 1: error.
+// M a multiple of 256.
 extern "C" int dle_gemm8_colstats_try(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
                                       int dtype, float* stats, hipStream_t stream) {
   if (!stats) return 0;

@@ -30,13 +30,6 @@
 #include "gemm_tiles.h"
 #include "gemm8_walk.h"
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_BWD = 3, ACT_ADD = 4, ACT_GELU_BWD = 5, ACT_TANH = 6,
-       ACT_TANH_BWD = 7, ACT_ADD_MASKED = 8, ACT_MUL = 9, ACT_GELU_DAUX = 10,
-       // the ReLU of a linear layer as ONE BIT per element (this kernel only: dle_gemm8_relu_bits_try / ..._bwd_bits_try):
-       // forward (EPI 1): bias + ReLU, aux RECEIVES the keep bits (bit (m N + n) & 7 of byte (m N + n) >> 3 = rounded output > 0);
-       // backward (EPI 2): C = product where the bit is set, aux = those bits, NO source tensor is read
-       ACT_RELU_BITS = 11, ACT_RELU_BWD_BITS = 12 };
-
 #define G8_HALF 8192                 // 16-bit elements per half-tile image (128 rows x 64 k)
 #define G8_BUF (4 * G8_HALF)         // one K tile: A0 | A1 | B0 | B1
 #define G8_STAGE_BYTES (2 * G8_BUF * 2)
@@ -76,6 +69,9 @@ struct Gemm8Args {
   int dbg_items;
 #endif
 };
+// the instantiation units' launchers (gemm8_epi1.hip, gemm8_epi2.hip; called from gemm8.hip): 0 for a combination they do not carry
+extern "C" int g8_launch_epi1(const Gemm8Args* p, int dt, int am, int bm, int act, int grid, hipStream_t stream);
+extern "C" int g8_launch_epi2(const Gemm8Args* p, int dt, int am, int bm, int act, int grid, hipStream_t stream);
 #ifdef G8_TIMING
 #define G8_STAMP(slot) do { if ((wave & 3) == 0 && lane == 0 && p.dbg && item_seq < p.dbg_items) \
     p.dbg[((((long long)blockIdx.x * 2 + wr) * p.dbg_items) + item_seq) * 4 + (slot)] = __builtin_readcyclecounter(); } while (0)
@@ -201,7 +197,7 @@ struct G8Lane {
   }
 };
 
-// (the same expressions, in the same order, as gelu_tanh2 / gelu_tanh2_d of gemm_dma.hip: results bit-identical to the tile kernels.
+// (the same expressions, in the same order, as gelu_tanh / gelu_tanh_d of gemm_family.h: results bit-identical to the tile kernels.
 //  An algebraically shorter form -- hp = 1 - r, 1 - tanh^2 = 4 r hp, 12 instead of 22 operations -- was measured: -7 % epilogue cycles
 //  on the GELU + side-output flavour, whose epilogue is bound by its two stores per block, and one rounding different, which moved
 //  a 2-element gradient of the 24-layer parity test across its bar; not kept.)

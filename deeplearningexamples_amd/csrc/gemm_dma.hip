@@ -24,17 +24,9 @@
 // (convolution forward / data-gradient: A(m,k) = X[n, p*stride - pad + r, q*stride - pad + s, c]).
 #include "gemm_tiles.h"
 
-#define BM 128
-#define BN 128
 #define SLAB_MODE(p) ((p).ws != nullptr)
 // operand stages (2 x 32 KiB); the fp32 epilogue staging tile 64 x (128+4) reuses them
 #define GEMM2_LDS_BYTES (2 * (BM * BK + BN * BK) * 2)
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_BWD = 3, ACT_ADD = 4, ACT_GELU_BWD = 5, ACT_TANH = 6,
-       ACT_TANH_BWD = 7,
-       ACT_ADD_MASKED = 8,   // C = acc + (bit ? mask_src : 0); aux = bit-packed keep bits of the addend (INPUT, 1 bit / element)
-       ACT_MUL = 9,          // C = acc * mask_src (e.g. the GELU derivative the forward GEMM left behind)
-       ACT_GELU_DAUX = 10 }; // C = gelu(v), aux = gelu'(v) (instead of the pre-activation): the backward is a plain multiply
 
 struct Gemm2Args {
   const unsigned short* A;
@@ -52,7 +44,7 @@ struct Gemm2Args {
   // batched mode (grid.z = batch): operand z = (zo, zi) = (z / batch_inner, z % batch_inner) starts at
   // base + zo * stride_outer + zi * stride_inner (elements) -- e.g. (sequence, head) slices of a [T, 3H] buffer
   int batch_inner, batch_count;
-  int debug_skip;        // reserved (profiling ablations)
+  int unused_pad;        // unused; keeps the layout of the fields below
   float* stats;          // per-tile-row column sums of the ROUNDED output: [tiles_m][2][N] (sum, sum of squares); NULL: off
   int force_small;       // keep the 128x128 tile (stats layout is indexed by 128-row tiles)
   int stats_sums;        // stats holds column SUMS only, one partial row per tile row: [tiles_m][N] (bias gradients); 0: [tiles_m][2][N]
@@ -63,21 +55,6 @@ struct Gemm2Args {
   int persist;           // 128x128 tile only: the grid is smaller than the tile list, a workgroup walks tiles bid, bid + grid, ...
   long long sa_o, sa_i, sb_o, sb_i, sc_o, sc_i;
 };
-
-__device__ __forceinline__ float gelu_tanh2(float x) {
-  const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float u = k0 * (x + k1 * x * x * x);
-  return 0.5f * x * (1.0f + fast_tanh(u));
-}
-// gelu(x) and d gelu / dx from one tanh
-__device__ __forceinline__ float gelu_tanh2_d(float x, float& d) {
-  const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float x2 = x * x;
-  const float th = fast_tanh(k0 * (x + k1 * x2 * x));
-  const float hp = 0.5f * (1.0f + th);
-  d = hp + 0.5f * x * (1.f - th * th) * k0 * (1.f + 3.f * k1 * x2);
-  return x * hp;
-}
 
 // Epilogue of 8 consecutive output columns of row m (v = alpha * accumulators): split-K partials, or bias /
 // activation / mask / addend math and the 16-byte stores of C (+ the pre-activation side output).
@@ -113,13 +90,13 @@ __device__ __forceinline__ void epi_store8(const Gemm2Args& p, float* v, int m, 
     for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
   } else if (p.act == ACT_GELU) {
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = gelu_tanh2(v[r]);
+    for (int r = 0; r < 8; ++r) v[r] = gelu_tanh(v[r]);
   } else if (p.act == ACT_TANH) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = fast_tanh(v[r]);
   } else if (p.act == ACT_GELU_DAUX) {
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = gelu_tanh2_d(v[r], pre[r]);
+    for (int r = 0; r < 8; ++r) v[r] = gelu_tanh_d(v[r], pre[r]);
   } else if (p.act == ACT_RELU_BWD || p.act == ACT_ADD || p.act == ACT_GELU_BWD || p.act == ACT_TANH_BWD ||
              p.act == ACT_ADD_MASKED || p.act == ACT_MUL) {
     ushort8_t sv = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -508,7 +485,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
       if constexpr (act == ACT_GELU_DAUX) {
         float dv[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = gelu_tanh2_d(v[r], dv[r]);
+        for (int r = 0; r < 8; ++r) v[r] = gelu_tanh_d(v[r], dv[r]);
         if (ax) *(ushort8_t*)(ax + it * step) = pack8<DT>(dv);   // derivative side output
       } else if (ax) {
         *(ushort8_t*)(ax + it * step) = pack8<DT>(v);            // pre-activation side output
@@ -518,7 +495,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
         for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
       } else if constexpr (act == ACT_GELU) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = gelu_tanh2(v[r]);
+        for (int r = 0; r < 8; ++r) v[r] = gelu_tanh(v[r]);
       } else if constexpr (act == ACT_TANH) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = fast_tanh(v[r]);
@@ -778,14 +755,12 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
 static int launch_gemm(const Gemm2Args& p_in, int in_dtype, int amode, int bmode, int batch, hipStream_t stream,
                        int* tile_rows_out = nullptr) {
   Gemm2Args p = p_in;
-  static const int gm_env = getenv("DLE_GEMM_GM") ? atoi(getenv("DLE_GEMM_GM")) : 8;
-  p.gm = gm_env > 0 ? gm_env : 8;
-  p.debug_skip = 0;
+  p.gm = dle_gemm_gm();
   p.batch_count = batch;
   const int ktiles = (p.K + BK - 1) / BK;
   const int kt_per_item = (ktiles + p.splitk - 1) / p.splitk;
   if (amode == 1 && bmode == 0) { dle_set_error("gemm: unsupported operand layout"); return 1; }
-  static const int big_mode = getenv("DLE_GEMM_BIG") ? atoi(getenv("DLE_GEMM_BIG")) : -1;
+  static const int big_mode = dle_env_int("DLE_GEMM_BIG", -1);
   const long long tiles_big = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256);
   const bool fits = amode <= 1 && bmode <= 1 && p.M >= 256 && p.N >= 256 &&
                     p.lda * 512 <= 0x7FFFFFFFLL && p.ldb * 512 <= 0x7FFFFFFFLL;
@@ -802,9 +777,8 @@ static int launch_gemm(const Gemm2Args& p_in, int in_dtype, int amode, int bmode
     dim3 grid((unsigned)tiles_big, p.splitk, batch > 0 ? batch : 1), block(512);
     // 128 KiB of operand stages + (when the device grants a workgroup the whole 160 KiB) 32 KiB for epilogue source rows
     const int lds_max = lim->lds_per_block;
-    static const int lds_src_mode = getenv("DLE_GEMM_LDS_SRC") ? atoi(getenv("DLE_GEMM_LDS_SRC")) : 1;
     const size_t lds_stages = 2 * (256 * BK + 256 * BK) * 2;
-    p.lds_src = lds_src_mode && lds_max >= (int)(lds_stages + 32768) && (long long)p.M * p.ldc * 2 < 0xFFFFFFE0LL;
+    p.lds_src = lds_max >= (int)(lds_stages + 32768) && (long long)p.M * p.ldc * 2 < 0xFFFFFFE0LL;
     const size_t lds_big = lds_stages + (lds_max >= (int)(lds_stages + 32768) ? 32768 : 0);
 #define GOBIG(DT, AM, BMODE) DLE_LAUNCH_LDS((gemm2_kernel<DT, AM, BMODE, 2, 1>), grid, block, lds_big, stream, p)
 #define PICKBIG(DT) do { if (amode == 0 && bmode == 0) GOBIG(DT, 0, 0); else if (amode == 0) GOBIG(DT, 0, 1); else GOBIG(DT, 1, 1); } while (0)
@@ -819,9 +793,8 @@ static int launch_gemm(const Gemm2Args& p_in, int in_dtype, int amode, int bmode
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     const size_t lds = GEMM2_LDS_BYTES;
     // persistent walk: two resident workgroups per CU, each prefetching its next tile under the current epilogue
-    static const int persist_mode = getenv("DLE_GEMM_PERSIST") ? atoi(getenv("DLE_GEMM_PERSIST")) : 1;
     const int resident = 2 * 256;
-    p.persist = persist_mode && amode <= 1 && bmode <= 1 && p.splitk == 1 && batch <= 0 && tiles > resident;
+    p.persist = amode <= 1 && bmode <= 1 && p.splitk == 1 && batch <= 0 && tiles > resident;
     dim3 grid(p.persist ? resident : tiles, p.splitk, batch > 0 ? batch : 1), block(256);
     // (a single-stage, 4-workgroups-per-CU variant for K <= 128 existed; with the hoisted epilogue it measured 2x
     //  SLOWER than this one -- 802816x256x64: 295 vs 144 us -- its 128-VGPR budget spilled; removed)
@@ -936,12 +909,8 @@ static bool launch_splitk_reduce_shallow(const float* ws, float* C, int M, int N
   return true;
 }
 
-extern "C" int dle_gemm8_try(const void* A, const void* B, void* C, void* aux, const float* bias, const void* src, int M, int N,
-                             int K, int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc, int in_dtype, int out_dtype,
-                             int act, int splitk, int accumulate, float alpha, float* ws, float* stats, hipStream_t stream);   // gemm8.hip
-
-// Returns 1 when the DMA kernel took the launch, 0 when the shape/alignment is outside its envelope
-// (caller falls back to gemm.hip), <0 / >1 on error.  Called from dle_gemm.
+// Route 4 of dle_gemm (gemm_route.hip): 0 when the shape / alignment is outside the envelope of the LDS-DMA kernels (the caller
+// falls back to gemm.hip).
 extern "C" int dle_gemm_dma_try(const void* A, const void* B, void* C, void* aux, const float* bias,
                                 const void* mask_src, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
                                 int a_kc, int b_kc, int in_dtype, int out_dtype, int act, int splitk,
@@ -976,12 +945,12 @@ extern "C" int dle_gemm_dma_try(const void* A, const void* B, void* C, void* aux
   if (!a_kc && b_kc) return 0;
   {
     // the big linear layers: the persistent ping-pong kernel of gemm8.hip (split-K only with slabs)
-    int r8 = 0;
+    bool on8 = false;
     if (splitk == 1 || p.ws)
-      r8 = dle_gemm8_try(A, B, C, aux, bias, mask_src, M, N, K, lda, ldb, ldc, a_kc, b_kc, in_dtype, out_dtype, act, splitk,
-                         accumulate, alpha, p.ws, nullptr, stream);
-    if (r8 > 1) return r8;
-    if (r8 == 0) { const int rc = launch_gemm(p, in_dtype, amode, bmode, 0, stream); if (rc) return rc + 1000; }
+      DLE_TRY(dle_gemm8_try(A, B, C, aux, bias, mask_src, M, N, K, lda, ldb, ldc, a_kc, b_kc, in_dtype, out_dtype, act, splitk,
+                            accumulate, alpha, p.ws, nullptr, stream),
+              on8 = true);
+    if (!on8) { const int rc = launch_gemm(p, in_dtype, amode, bmode, 0, stream); if (rc) return rc + 1000; }
   }
   if (p.ws) {
     long long items = ((long long)M * N + 3) / 4;
@@ -1029,14 +998,13 @@ __global__ __launch_bounds__(256) void colsum_fold_kernel(const float* __restric
 // stored GELU derivative: LanguageModeling/BERT/modeling.py:130-160 backward of bias_gelu).  The separate column-sum pass re-read
 // every such gradient the step had just written (114 us per DLRM step at batch 65536, 1.06 ms per BERT-Large step).  One
 // partial row per tile row, folded in a fixed order.  1: launched; 0: outside the envelope (the caller runs dle_gemm +
-// dle_colsum); > 1: error.
+// dle_colsum); anything else: error.
 extern "C" int dle_gemm_colsum(const void* A, const void* B, void* C, const void* src, float* colsum_out, int M, int N, int K,
                                int64_t lda, int64_t ldb, int64_t ldc, int dtype, int act, int accumulate_colsum, void* workspace,
                                int64_t workspace_bytes, hipStream_t stream) {
   const void* mask_src = src;
   if (act != ACT_RELU_BWD && act != ACT_MUL) return 0;
-  static const int mode = getenv("DLE_GEMM_COLSUM") ? atoi(getenv("DLE_GEMM_COLSUM")) : 1;
-  if (!mode || !A || !B || !C || !mask_src || !colsum_out || !workspace) return 0;
+  if (!A || !B || !C || !mask_src || !colsum_out || !workspace) return 0;
   if (dtype != DLE_F16 && dtype != DLE_BF16) return 0;
   const bool al = ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)mask_src) | ((uintptr_t)workspace)) & 15) == 0 &&
                   (lda & 7) == 0 && (ldb & 7) == 0 && (ldc & 7) == 0;
@@ -1053,11 +1021,10 @@ extern "C" int dle_gemm_colsum(const void* A, const void* B, void* C, const void
   int tile_rows = 0;
   {
     // ping-pong kernel: two partial rows per 256-row tile row (one per wavefront row group) = ceil(M / 128) rows when 256 | M
-    const int r8 = dle_gemm8_try(A, B, C, nullptr, nullptr, mask_src, M, N, K, lda, ldb, ldc, 1, 0, dtype, dtype, act, 1, 0, 1.0f,
-                                 nullptr, (float*)workspace, stream);
-    if (r8 > 1) return r8;
-    if (r8 == 1) tile_rows = 128;
-    else { const int rc = launch_gemm(p, dtype, 0, 1, 0, stream, &tile_rows); if (rc) return rc + 1000; }
+    DLE_TRY(dle_gemm8_try(A, B, C, nullptr, nullptr, mask_src, M, N, K, lda, ldb, ldc, 1, 0, dtype, dtype, act, 1, 0, 1.0f, nullptr,
+                          (float*)workspace, stream),
+            tile_rows = 128);
+    if (!tile_rows) { const int rc = launch_gemm(p, dtype, 0, 1, 0, stream, &tile_rows); if (rc) return rc + 1000; }
   }
   hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const float*)workspace, colsum_out, N,
                      (M + tile_rows - 1) / tile_rows, accumulate_colsum);
@@ -1065,9 +1032,6 @@ extern "C" int dle_gemm_colsum(const void* A, const void* B, void* C, const void
   if (e != hipSuccess) { dle_set_error("colsum_fold launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
   return 1;
 }
-
-extern "C" int dle_gemm8_relu_bwd_bits_try(const void* dY, const void* W, void* dX, const void* bits, float* colsum_partial, int M,
-                                           int N, int K, int64_t lddy, int64_t ldw, int dtype, hipStream_t stream);   // gemm8.hip
 
 // dle_gemm_colsum with the ReLU mask of the layer below as ONE BIT per element (the keep bits dle_gemm8_relu_bits_try left
 // beside that layer's forward output) instead of the 16-bit activation: C [M, N] = (A [M, K] B [K, N]) where the bit is set,
@@ -1079,8 +1043,9 @@ extern "C" int dle_gemm_colsum_bits(const void* A, const void* B, void* C, const
                                     int64_t workspace_bytes, hipStream_t stream) {
   if (!A || !B || !C || !bits || !colsum_out || !workspace) return 0;
   if ((M & 255) != 0 || workspace_bytes < (long long)((M + 127) / 128) * N * 4) return 0;
-  const int r8 = dle_gemm8_relu_bwd_bits_try(A, B, C, bits, (float*)workspace, M, N, K, lda, ldb, dtype, stream);
-  if (r8 != 1) return r8;
+  bool launched = false;
+  DLE_TRY(dle_gemm8_relu_bwd_bits_try(A, B, C, bits, (float*)workspace, M, N, K, lda, ldb, dtype, stream), launched = true);
+  if (!launched) return 0;
   hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const float*)workspace, colsum_out, N,
                      (M + 127) / 128, accumulate_colsum);
   hipError_t e = hipGetLastError();
@@ -1092,14 +1057,6 @@ extern "C" int dle_gemm_colsum_bits(const void* A, const void* B, void* C, const
 // ---- convolutions as implicit GEMM (NHWC activations, KRSC weights, 16-bit in, fp32 accumulate) -------------
 // Replace cuDNN's conv fwd / bwd-data / bwd-filter behind nn.Conv2d(bias=False)
 // (Classification/ConvNets/image_classification/models/common.py:31-60, resnet.py:126-175).
-extern "C" int dle_conv3x3_try(const void* x, const void* w, void* y, float* stats, long long stats_bytes, int N, int H,
-                               int W, int C, int Ko, int dgrad, int dtype, hipStream_t stream);   // conv3x3.hip
-extern "C" int dle_conv3x3_tiles(int N, int H, int W);                                          // conv3x3.hip
-
-static int conv_launch(Gemm2Args& p, int in_dtype, int amode, int bmode, hipStream_t stream) {
-  return launch_gemm(p, in_dtype, amode, bmode, 0, stream);
-}
-
 static int conv_check(const char* what, int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad,
                       int P, int Q, int dtype) {
   DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "%s: 16-bit dtypes only (got %d)", what, dtype);
@@ -1119,25 +1076,18 @@ extern "C" int dle_conv2d_fwd(const void* x, const void* w, void* y, const float
   if (int rc = conv_check("conv2d_fwd", N, H, W, C, Ko, R, S, stride, pad, P, Q, dtype)) return rc;
   DLE_CHECK_ARG(x && w && y, "conv2d_fwd: null pointer");
   DLE_CHECK_ARG(act == ACT_NONE || act == ACT_RELU, "conv2d_fwd: unsupported epilogue %d", act);
-  if (R == 3 && S == 3 && stride == 1 && pad == 1 && !bias && act == ACT_NONE && out_dtype == dtype) {
-    const int rc = dle_conv3x3_try(x, w, y, nullptr, 0, N, H, W, C, Ko, 0, dtype, stream);   // halo-tile kernel
-    if (rc == 1) return 0;
-    if (rc > 1) return rc;
-  }
+  if (R == 3 && S == 3 && stride == 1 && pad == 1 && !bias && act == ACT_NONE && out_dtype == dtype)
+    DLE_TRY(dle_conv3x3_try(x, w, y, nullptr, 0, N, H, W, C, Ko, 0, dtype, stream), return 0);   // halo-tile kernel
   Gemm2Args p = {};
   p.A = (const unsigned short*)x; p.B = (const unsigned short*)w; p.C = y; p.bias = bias;
   p.M = N * P * Q; p.N = Ko; p.K = R * S * C; p.lda = 0; p.ldb = (long long)R * S * C; p.ldc = Ko;
   p.out_dtype = out_dtype; p.act = act; p.splitk = 1; p.accumulate = 0; p.alpha = 1.f;
   p.cg = make_geom(H, W, C, P, Q, R, S, stride, pad, Ko);
-  return conv_launch(p, dtype, 2, 0, stream);
+  return launch_gemm(p, dtype, 2, 0, 0, stream);
 }
 
-extern "C" int dle_gemm8_colstats_try(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-                                      int dtype, float* stats, hipStream_t stream);   // gemm8.hip
-extern "C" int dle_gemm_expand_groups(int M, int N, int K);                // gemm_expand.hip
-extern "C" int dle_gemm_expand_try(const void* A, const void* B, void* C, const void* src, const void* bits, float* stats, int M,
-                                   int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_kc, int in_dtype, int out_dtype,
-                                   int act, hipStream_t stream);
+// row limit of the ping-pong kernel in dle_conv2d_fwd_colstats: the 14 x 14 and 7 x 7 stages at batch 256
+static const long long CONV_STATS_GEMM8_MAX_M = 65536;
 
 // dle_conv2d_fwd (no bias / activation) that ALSO leaves, per 128-row tile of the [N*P*Q, Ko] output, the column sums
 // and sums of squares of the ROUNDED output in col_partial[tile_row][2][Ko] -- the BatchNorm that follows gets its
@@ -1156,34 +1106,21 @@ extern "C" int dle_conv2d_fwd_colstats(const void* x, const void* w, void* y, in
   *groups = g;
   // the halo kernel writes one row per 256 PADDED slots, ceil(N (H+1) (W+2) / 256): more than the ceil(M / 128) rows the caller
   // had to provide when H is small (H = 1: 2 (W+2) slots per 128-row tile of W pixels); it only runs when the buffer holds them
-  if (R == 3 && S == 3 && stride == 1 && pad == 1 && col_partial_bytes >= (long long)dle_conv3x3_tiles(N, H, W) * 2 * Ko * 4) {
-    const int rc = dle_conv3x3_try(x, w, y, col_partial, col_partial_bytes, N, H, W, C, Ko, 0, dtype, stream);
-    if (rc == 1) { *groups = (int)(((long long)N * (H + 1) * (W + 2) + 255) / 256); return 0; }
-    if (rc > 1) return rc;
-  }
+  if (R == 3 && S == 3 && stride == 1 && pad == 1 && col_partial_bytes >= (long long)dle_conv3x3_tiles(N, H, W) * 2 * Ko * 4)
+    DLE_TRY(dle_conv3x3_try(x, w, y, col_partial, col_partial_bytes, N, H, W, C, Ko, 0, dtype, stream),
+            *groups = (int)(((long long)N * (H + 1) * (W + 2) + 255) / 256); return 0);
   const bool plain = R == 1 && S == 1 && stride == 1 && pad == 0;
-  if (plain && M < 0x7FFFFFFF && (M & 255) == 0) {
-    // the deep stages (14 x 14, 7 x 7: M <= 65536 rows, K >= 128): the persistent ping-pong kernel with the statistics in its
-    // register epilogue (gemm8_kernel.h EPI 3) -- the streaming / tile kernels run these shapes at 0.4 of their HBM floor.
-    // DLE_CONV_STATS_GEMM8=0 pins the older kernels; DLE_CONV_STATS_GEMM8_MAXM moves the row limit (A/B measurements).
-    static const int g8on = getenv("DLE_CONV_STATS_GEMM8") ? atoi(getenv("DLE_CONV_STATS_GEMM8")) : 1;
-    static const long long g8maxm = getenv("DLE_CONV_STATS_GEMM8_MAXM") ? atoll(getenv("DLE_CONV_STATS_GEMM8_MAXM")) : 65536;
-    if (g8on && M <= g8maxm && C >= 128 && Ko >= 256) {
-      const int rc = dle_gemm8_colstats_try(x, w, y, (int)M, Ko, C, C, C, Ko, dtype, col_partial, stream);
-      if (rc == 1) { *groups = g; return 0; }
-      if (rc > 1) return rc;
-    }
-  }
+  // the deep stages (14 x 14, 7 x 7: M <= 65536 rows, K >= 128): the persistent ping-pong kernel with the statistics in its
+  // register epilogue (gemm8_kernel.h EPI 3) -- the streaming / tile kernels run these shapes at 0.4 of their HBM floor
+  if (plain && M < 0x7FFFFFFF && (M & 255) == 0 && M <= CONV_STATS_GEMM8_MAX_M && C >= 128 && Ko >= 256)
+    DLE_TRY(dle_gemm8_colstats_try(x, w, y, (int)M, Ko, C, C, C, Ko, dtype, col_partial, stream), *groups = g; return 0);
   if (plain && M < 0x7FFFFFFF) {
     // channel-widening 1x1 convolutions: the streaming kernel of gemm_expand.hip (one partial row per workgroup group)
-    const char* pin = getenv("DLE_GEMM_EXPAND");                          // probes / tests: "0" pins the tile kernels
-    static const int kmin = getenv("DLE_EXPAND_STATS_KMIN") ? atoi(getenv("DLE_EXPAND_STATS_KMIN")) : 64;
+    static const int kmin = dle_env_int("DLE_EXPAND_STATS_KMIN", 64);
     const int eg = dle_gemm_expand_groups((int)M, Ko, C);
-    if ((!pin || atoi(pin) != 0) && C >= kmin && col_partial_bytes >= (long long)eg * 2 * Ko * 4) {
-      const int rc = dle_gemm_expand_try(x, w, y, nullptr, nullptr, col_partial, (int)M, Ko, C, C, C, Ko, 1, dtype, dtype, 0, stream);
-      if (rc == 1) { *groups = eg; return 0; }
-      if (rc > 1) return rc;
-    }
+    if (dle_gemm_expand_enabled() && C >= kmin && col_partial_bytes >= (long long)eg * 2 * Ko * 4)
+      DLE_TRY(dle_gemm_expand_try(x, w, y, nullptr, nullptr, col_partial, (int)M, Ko, C, C, C, Ko, 1, dtype, dtype, EX_ACT_NONE, stream),
+              *groups = eg; return 0);
   }
   Gemm2Args p = {};
   p.A = (const unsigned short*)x; p.B = (const unsigned short*)w; p.C = y;
@@ -1192,7 +1129,7 @@ extern "C" int dle_conv2d_fwd_colstats(const void* x, const void* w, void* y, in
   p.stats = col_partial; p.force_small = 1;
   p.lda = plain ? C : 0;
   p.cg = make_geom(H, W, C, P, Q, R, S, stride, pad, Ko);
-  return conv_launch(p, dtype, plain ? 0 : 2, 0, stream);
+  return launch_gemm(p, dtype, plain ? 0 : 2, 0, 0, stream);
 }
 
 // dx[N,H,W,C] = conv_transpose(dy[N,P,Q,Ko], w[Ko,R,S,C]) (+ addend[N,H,W,C] when non-NULL)
@@ -1201,22 +1138,16 @@ extern "C" int dle_conv2d_dgrad(const void* dy, const void* w, void* dx, const v
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   if (int rc = conv_check("conv2d_dgrad", N, H, W, C, Ko, R, S, stride, pad, P, Q, dtype)) return rc;
   DLE_CHECK_ARG(dy && w && dx, "conv2d_dgrad: null pointer");
-  if (R == 3 && S == 3 && stride == 1 && pad == 1 && !addend) {
-    const int rc = dle_conv3x3_try(dy, w, dx, nullptr, 0, N, H, W, C, Ko, 1, dtype, stream);
-    if (rc == 1) return 0;
-    if (rc > 1) return rc;
-  }
+  if (R == 3 && S == 3 && stride == 1 && pad == 1 && !addend)
+    DLE_TRY(dle_conv3x3_try(dy, w, dx, nullptr, 0, N, H, W, C, Ko, 1, dtype, stream), return 0);
   Gemm2Args p = {};
   p.A = (const unsigned short*)dy; p.B = (const unsigned short*)w; p.C = dx;
   p.mask_src = (const unsigned short*)addend;
   p.M = N * H * W; p.N = C; p.K = R * S * Ko; p.lda = 0; p.ldb = 0; p.ldc = C;
   p.out_dtype = dtype; p.act = addend ? ACT_ADD : ACT_NONE; p.splitk = 1; p.accumulate = 0; p.alpha = 1.f;
   p.cg = make_geom(H, W, C, P, Q, R, S, stride, pad, Ko);
-  return conv_launch(p, dtype, 4, 5, stream);
+  return launch_gemm(p, dtype, 4, 5, 0, stream);
 }
-
-extern "C" int dle_conv3x3_wgrad_try(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int dtype,
-                                     int accumulate, void* workspace, int64_t workspace_bytes, hipStream_t stream);   // conv3x3_wgrad.hip
 
 // dw[Ko,R,S,C] (fp32) (+)= sum over pixels dy[N,P,Q,Ko]^T im2col(x[N,H,W,C]); workspace: split-K slabs.
 extern "C" int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int R,
@@ -1225,12 +1156,9 @@ extern "C" int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N,
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   if (int rc = conv_check("conv2d_wgrad", N, H, W, C, Ko, R, S, stride, pad, P, Q, dtype)) return rc;
   DLE_CHECK_ARG(dy && x && dw, "conv2d_wgrad: null pointer");
-  if (R == 3 && S == 3 && stride == 1 && pad == 1) {
-    // halo-tile kernel (conv3x3_wgrad.hip): the nine taps share one activation patch and one dy tile per pixel tile
-    const int rc = dle_conv3x3_wgrad_try(dy, x, dw, N, H, W, C, Ko, dtype, accumulate, workspace, workspace_bytes, stream);
-    if (rc == 1) return 0;
-    if (rc > 1) return rc;
-  }
+  // halo-tile kernel (conv3x3_wgrad.hip): the nine taps share one activation patch and one dy tile per pixel tile
+  if (R == 3 && S == 3 && stride == 1 && pad == 1)
+    DLE_TRY(dle_conv3x3_wgrad_try(dy, x, dw, N, H, W, C, Ko, dtype, accumulate, workspace, workspace_bytes, stream), return 0);
   Gemm2Args p = {};
   p.A = (const unsigned short*)dy; p.B = (const unsigned short*)x; p.C = dw;
   p.M = Ko; p.N = R * S * C; p.K = N * P * Q; p.lda = Ko; p.ldb = 0; p.ldc = (long long)R * S * C;
@@ -1248,7 +1176,7 @@ extern "C" int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N,
       if (e != hipSuccess) { dle_set_error("conv2d_wgrad memset: %s", hipGetErrorString(e)); return (int)e; }
     }
   }
-  if (int rc = conv_launch(p, dtype, 1, 3, stream)) return rc;
+  if (int rc = launch_gemm(p, dtype, 1, 3, 0, stream)) return rc;
   if (p.ws) {
     long long g = (((long long)p.M * p.N + 3) / 4 + 15) / 16;         // 16 float4 elements per workgroup trip
     if (g > 4096) g = 4096;

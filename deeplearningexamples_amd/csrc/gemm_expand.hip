@@ -341,26 +341,25 @@ void gemm_expand_kernel(ExpandArgs p) {
 static int ex_rows_per_tile(int K) { return K > 128 ? 128 : 64; }
 extern "C" int dle_gemm_expand_groups(int M, int N, int K) {
   const int tm = ex_rows_per_tile(K), row_tiles = (M + tm - 1) / tm, col_tiles = N / EX_TN;
-  static const int per_cu_env = getenv("DLE_EXPAND_WG_PER_CU") ? atoi(getenv("DLE_EXPAND_WG_PER_CU")) : 0;   // probe knob
-  const int per_cu = per_cu_env > 0 ? per_cu_env : (K > 128 ? 2 : 4);  // workgroups a CU holds at once (16 waves per CU)
+  const int per_cu = K > 128 ? 2 : 4;                                  // workgroups a CU holds at once (16 waves per CU)
   const int resident = 256 * per_cu;
   int groups = (resident + col_tiles - 1) / (col_tiles > 0 ? col_tiles : 1);
   if (groups > row_tiles) groups = row_tiles;
   return (groups + 7) / 8 * 8;                                         // XCD-aware dealing (see the kernel); idle groups run no tile
 }
 
-// 1: launched; 0: outside the envelope (the caller goes on to the tile kernels); > 1: error.
-// act: 0 none, 1 DLE_ACT_ADD, 2 DLE_ACT_ADD_MASKED (bits = keep bits of the addend, bit (m ldc + n) & 7 of byte (m ldc + n) >> 3).
+// 0: outside the envelope (the caller goes on to the tile kernels).
+// act: EX_ACT_NONE, EX_ACT_ADD (DLE_ACT_ADD), EX_ACT_ADD_MASKED (DLE_ACT_ADD_MASKED; bits = keep bits of the addend, bit (m ldc + n) & 7 of byte (m ldc + n) >> 3).
 extern "C" int dle_gemm_expand_try(const void* A, const void* B, void* C, const void* src, const void* bits, float* stats, int M,
                                    int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_kc, int in_dtype, int out_dtype,
                                    int act, hipStream_t stream) {
   if (M < 4096 || (K != 64 && K != 128 && K != 256) || (N % EX_TN) != 0 || N < 2 * K || out_dtype != in_dtype) return 0;
   if (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)src)) & 15) != 0 || (lda & 7) || (ldb & 7) || (ldc & 7)) return 0;
-  if (act < 0 || act > 2) return 0;
-  if (act == 2 && !bits) return 0;
+  if (act < EX_ACT_NONE || act > EX_ACT_ADD_MASKED) return 0;
+  if (act == EX_ACT_ADD_MASKED && !bits) return 0;
   // the masked epilogue reads a row's 16 keep bytes with ONE 16-byte load at bits + ((m ldc + n0) >> 3): needs ldc % 128 == 0 and
   // a 16-byte aligned bit plane (other pitches go to the tile kernel's per-byte form)
-  if (act == 2 && ((ldc % EX_TN) != 0 || (((uintptr_t)bits) & 15) != 0)) return 0;
+  if (act == EX_ACT_ADD_MASKED && ((ldc % EX_TN) != 0 || (((uintptr_t)bits) & 15) != 0)) return 0;
   if (act && !src) return 0;
   ExpandArgs p = {(const unsigned short*)A, (const unsigned short*)B, (unsigned short*)C, (const unsigned short*)src,
                   (const unsigned char*)bits, stats, M, N, K, (long long)lda, (long long)ldb, (long long)ldc, b_kc, 0, 0, 0};
@@ -377,10 +376,10 @@ extern "C" int dle_gemm_expand_try(const void* A, const void* B, void* C, const 
   } while (0)
 #define PICK_ACT(DT, KS)                                              \
   do {                                                                \
-    if (stats) { if (act != 0) return 0; GO(DT, KS, 0, true); }       \
-    else if (act == 0) GO(DT, KS, 0, false);                          \
-    else if (act == 1) GO(DT, KS, 1, false);                          \
-    else GO(DT, KS, 2, false);                                        \
+    if (stats) { if (act != EX_ACT_NONE) return 0; GO(DT, KS, EX_ACT_NONE, true); } \
+    else if (act == EX_ACT_NONE) GO(DT, KS, EX_ACT_NONE, false);                    \
+    else if (act == EX_ACT_ADD) GO(DT, KS, EX_ACT_ADD, false);                      \
+    else GO(DT, KS, EX_ACT_ADD_MASKED, false);                                      \
   } while (0)
 #define PICK_K(DT)                                   \
   do {                                               \
@@ -406,12 +405,10 @@ extern "C" int dle_gemm_expand_masked_bnred(const void* A, const void* B, void* 
                                             const void* bits2, const float* mean2, const float* rstd2, float* partial,
                                             int64_t partial_bytes, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
                                             int b_kc, int dtype, hipStream_t stream) {
-  static const char* pin = getenv("DLE_GEMM_EXPAND");
-  if (pin && atoi(pin) == 0) return 0;
+  if (!dle_gemm_expand_enabled()) return 0;
   // (K = 256 is built and correct, but its 8-wave workgroup spills and runs slower than the two launches: 104 us against 60 + 39 at
   //  50176 x 1024 x 256; DLE_GEMM_BNRED_K256=1 lets it through for measurement)
-  const char* k256e = getenv("DLE_GEMM_BNRED_K256");                     // (read per call: tests switch it inside one process)
-  const int k256 = k256e ? atoi(k256e) : 0;
+  const int k256 = dle_env_int("DLE_GEMM_BNRED_K256", 0);              // (read per call: tests switch it inside one process)
   if (M < 4096 || (K != 64 && K != 128 && !(K == 256 && k256)) || (N % EX_TN) != 0 || N < 2 * K) return 0;
   if (dtype != DLE_F16 && dtype != DLE_BF16) return 0;
   if (!A || !B || !C || !src || !bits || !t2 || !bits2 || !mean2 || !rstd2 || !partial) return 0;
@@ -454,8 +451,7 @@ extern "C" int dle_gemm_expand_add_up2(const void* A, const void* B, void* C, co
   if ((H & 1) || (W & 1) || H <= 0 || W <= 0 || (M % (H * W)) != 0 || !compact) return 0;
   if (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)compact)) & 15) != 0 || (lda & 7) || (ldb & 7) || (ldc & 7) ||
       (ld_compact & 7)) return 0;
-  static const char* pin = getenv("DLE_GEMM_EXPAND");
-  if (pin && atoi(pin) == 0) return 0;
+  if (!dle_gemm_expand_enabled()) return 0;
   ExpandArgs p = {(const unsigned short*)A, (const unsigned short*)B, (unsigned short*)C, (const unsigned short*)compact, nullptr,
                   nullptr, M, N, K, (long long)lda, (long long)ldb, (long long)ldc, b_kc, 0, 0, 0};
   p.dHW = make_fastdiv(H * W); p.dW = make_fastdiv(W);

@@ -262,11 +262,11 @@ __global__ __launch_bounds__(NW * 64) void gemm_smallm_kernel(SmallMArgs p) {
   }
 }
 
-// 1: launched; 0: outside the envelope (the caller goes on to the other kernels); > 1: error.
+// 0: outside the envelope (the caller goes on to the other kernels).
 extern "C" int dle_gemm_smallm_try(const void* A, const void* B, void* C, const float* bias, const void* src, int M, int N, int K,
                                    int64_t lda, int64_t ldb, int64_t ldc, int in_dtype, int out_dtype, int act_add, int accumulate,
                                    float alpha, hipStream_t stream) {
-  static const int mode = getenv("DLE_GEMM_SMALLM") ? atoi(getenv("DLE_GEMM_SMALLM")) : 1;
+  static const int mode = dle_env_int("DLE_GEMM_SMALLM", 1);
   if (!mode || M < 1 || M > 256 || N < 8 || K < 8) return 0;
   if (((((uintptr_t)A) | ((uintptr_t)B)) & 15) != 0 || (lda & 7) != 0 || (ldb & 7) != 0 || (K & 7) != 0) return 0;
   if ((long long)M * lda * 2 >= 0xFFFFFFE0LL || (long long)N * ldb * 2 >= 0xFFFFFFE0LL) return 0;
@@ -286,13 +286,10 @@ extern "C" int dle_gemm_smallm_try(const void* A, const void* B, void* C, const 
   {
     // tools/probes/smallm_policy.py: DLE_GEMM_SMALLM_TN = 16 | 32 pins the tile, DLE_GEMM_SMALLM_NST the ring depth (read per
     // call)
-    const char* pin = getenv("DLE_GEMM_SMALLM_TN");
-    if (pin) {
-      const int tn = atoi(pin);
-      if (tn == 16) wide = false;
-      else if (tn == 32 && N > 16) wide = true;
-      if (getenv("DLE_GEMM_SMALLM_NST")) nst_pin = atoi(getenv("DLE_GEMM_SMALLM_NST"));
-    }
+    const int tn = dle_env_int("DLE_GEMM_SMALLM_TN", 0);
+    if (tn == 16) wide = false;
+    else if (tn == 32 && N > 16) wide = true;
+    nst_pin = dle_env_int("DLE_GEMM_SMALLM_NST", 0);
   }
   const int tiles = wide ? t32 : t16;
   const bool deep = tiles <= 256;                 // at most one workgroup per CU: four stages; else three (two workgroups per CU)

@@ -1,11 +1,8 @@
 // Shared building blocks of the LDS-DMA fed MFMA kernels (gemm_dma.hip, conv3x3.hip): constant division, the
 // implicit-GEMM geometry, the per-operand DMA tile loaders, MFMA fragment reads out of the swizzled LDS images.
 #pragma once
-#include "common.h"
-#include <stdlib.h>
+#include "gemm_family.h"
 #include <type_traits>
-
-#define BK 64
 
 // Division by a launch-time constant as multiply-high + shift (exact for 0 <= n < 2^31): the im2col loaders
 // decompose k -> (tap, channel) and pixel -> (n, p, q) for every DMA piece of every K tile; with generic integer

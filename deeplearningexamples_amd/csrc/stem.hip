@@ -168,8 +168,7 @@ __global__ __launch_bounds__(256) void stem7_fwd_kernel(StemArgs a) {
 }
 
 static int stem_fwd_workgroups(int items) {
-  static const int per_cu = getenv("DLE_STEM_FWD_WG_PER_CU") ? atoi(getenv("DLE_STEM_FWD_WG_PER_CU")) : 2;
-  const int cap = 256 * (per_cu > 0 ? per_cu : 2);          // 238 registers: two workgroups per CU
+  const int cap = 256 * 2;                                  // 238 registers: two workgroups per CU
   return items < cap ? items : cap;
 }
 

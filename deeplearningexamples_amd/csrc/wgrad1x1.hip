@@ -187,7 +187,7 @@ hipError_t wgrad1x1_fold(const float* ws, float* dw, long long total4, int G, in
   return hipGetLastError();
 }
 
-static int g_w1_mode = -1;
+static int g_w1_mode = -1;               // 0: off (A/B harnesses); anything else: on where it applies
 extern "C" int dle_wgrad1x1_mode(int mode) {
   const int old = g_w1_mode;
   g_w1_mode = mode;
@@ -200,8 +200,7 @@ extern "C" int64_t dle_wgrad1x1_workspace(void) { return 64LL << 20; }
 // workspace of ONE shape (bytes), 0 when (M, Ko, C) is outside the kernel's envelope -- so that a caller does not grow its
 // per-stream scratch to the 64 MB maximum for shapes the kernel declines
 extern "C" int64_t dle_wgrad1x1_workspace_for(int M, int Ko, int C) {
-  static const int env_mode = getenv("DLE_WGRAD1X1") ? atoi(getenv("DLE_WGRAD1X1")) : -1;
-  if (g_w1_mode == 0 || (g_w1_mode < 0 && env_mode == 0)) return 0;
+  if (g_w1_mode == 0) return 0;
   if (M < 8192 || (long long)M * (Ko > C ? Ko : C) * 2 >= 0xFFFFFFE0LL) return 0;
   int tg = 0, wgs = 0;
 #define W1_CFG(KOv, CCv, TGv, WGSv) if (Ko == KOv && C == CCv) { tg = TGv; wgs = WGSv; }
@@ -214,11 +213,10 @@ extern "C" int64_t dle_wgrad1x1_workspace_for(int M, int Ko, int C) {
   return (int64_t)wgs * Ko * C * 4;
 }
 
-// 1: launched; 0: outside the envelope (the caller uses the split-K tile GEMM); > 1: error.
+// The `*_try` convention of gemm_family.h; 0: outside the envelope (the caller uses the split-K tile GEMM).
 extern "C" int dle_wgrad1x1_try(const void* dy, const void* x, float* dw, int M, int Ko, int C, int dtype, int accumulate,
                                 void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  static const int env_mode = getenv("DLE_WGRAD1X1") ? atoi(getenv("DLE_WGRAD1X1")) : -1;
-  if (g_w1_mode == 0 || (g_w1_mode < 0 && env_mode == 0)) return 0;
+  if (g_w1_mode == 0) return 0;
   if (dtype != DLE_F16 && dtype != DLE_BF16) return 0;
   if (M < 8192 || (long long)M * (Ko > C ? Ko : C) * 2 >= 0xFFFFFFE0LL) return 0;
   if (((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dw) | ((uintptr_t)workspace)) & 15) != 0 || !workspace) return 0;
