@@ -17,6 +17,7 @@
 // These are pure HBM-streaming kernels: 16 B per lane accesses, wave64 shuffle reductions.
 // Algorithmic bytes / parameter: l2norm e_g; stage1 reads g+p+m+v, writes g+m+v; stage2 reads g+p, writes p(+p16).
 #include "common.h"
+#include <climits>
 
 #define MT_BLOCK 512
 
@@ -621,15 +622,32 @@ extern "C" int64_t dle_mt_table_fill(int64_t* table_host, int n_tensors, int n_l
   return acc;
 }
 
+// The table rule of include/dle_mi355x.h, checked by every entry point before anything is launched: chunk is a positive multiple
+// of 4 (a ragged 4-group then exists only at a tensor's end, and no chunk of a 16-byte aligned tensor starts misaligned), and
+// total_chunks is a grid size (0 .. INT_MAX).
+static bool mt_args_ok(const char* who, int chunk, int64_t total_chunks) {
+  if (chunk <= 0 || chunk % 4 != 0) {
+    dle_set_error("%s: chunk must be a positive multiple of 4 (got %d)", who, chunk);
+    return false;
+  }
+  if (total_chunks < 0 || total_chunks > (int64_t)INT_MAX) {
+    dle_set_error("%s: total_chunks %lld outside [0, INT_MAX]", who, (long long)total_chunks);
+    return false;
+  }
+  return true;
+}
+#define MT_CHECK_TABLE(who) do { if (!mt_args_ok(who, chunk, total_chunks)) return -1; } while (0)
+
 // partial: device scratch of >= total_chunks floats.
 extern "C" int dle_mt_l2norm(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, int dtype,
                              float* partial, float* ret, float* ret_per_tensor, int per_tensor, int* noop_flag,
                              hipStream_t stream) {
   DLE_CHECK_ARG(table_dev && partial && ret, "mt_l2norm: null pointer");
-  DLE_CHECK_ARG(!per_tensor || ret_per_tensor, "mt_l2norm: per_tensor needs ret_per_tensor");
-  DLE_CHECK_ARG(chunk > 0 && chunk % 4 == 0, "mt_l2norm: chunk must be a positive multiple of 4");
-  if (n_tensors == 0 || total_chunks == 0) {
+  DLE_CHECK_ARG(!per_tensor || ret_per_tensor || n_tensors == 0, "mt_l2norm: per_tensor needs ret_per_tensor");
+  MT_CHECK_TABLE("mt_l2norm");
+  if (n_tensors == 0 || total_chunks == 0) {   // nothing to sum (no tensor, or every tensor empty): every norm asked for is 0
     hipError_t e = hipMemsetAsync(ret, 0, 4, stream);
+    if (e == hipSuccess && per_tensor && n_tensors > 0) e = hipMemsetAsync(ret_per_tensor, 0, 4 * (size_t)n_tensors, stream);
     return e == hipSuccess ? 0 : (int)e;
   }
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
@@ -650,6 +668,7 @@ extern "C" int dle_mt_lamb_stage1(const int64_t* table_dev, int n_tensors, int64
                                   const float* global_grad_norm, const float* max_grad_norm,
                                   const float* inv_scale, hipStream_t stream) {
   DLE_CHECK_ARG(table_dev && step_dev && global_grad_norm && max_grad_norm && inv_scale, "mt_lamb_stage1: null pointer");
+  MT_CHECK_TABLE("mt_lamb_stage1");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
 #define GO(GT) hipLaunchKernelGGL((mt_lamb_stage1<GT, false>), grid, block, 0, stream, (const long long*)table_dev, n_tensors, chunk, (int*)noop_flag, beta1, beta2, beta3, step_dev, bias_correction, eps, mode, weight_decay, global_grad_norm, max_grad_norm, inv_scale, (float*)nullptr, (float*)nullptr)
@@ -671,10 +690,16 @@ extern "C" int dle_mt_lamb_stage1_norms(const int64_t* table_dev, int n_tensors,
                                         const int* step_dev, int bias_correction, float eps, int mode, float weight_decay,
                                         const float* global_grad_norm, const float* max_grad_norm, const float* inv_scale,
                                         float* partial, float* param_norm, float* update_norm, hipStream_t stream) {
-  DLE_CHECK_ARG(table_dev && step_dev && global_grad_norm && max_grad_norm && inv_scale && partial && param_norm && update_norm,
-                "mt_lamb_stage1_norms: null pointer");
+  DLE_CHECK_ARG(table_dev && step_dev && global_grad_norm && max_grad_norm && inv_scale && partial &&
+                ((param_norm && update_norm) || n_tensors == 0), "mt_lamb_stage1_norms: null pointer");
   DLE_CHECK_ARG(weight_decay != 0.f, "mt_lamb_stage1_norms: the stage reads the parameters only under weight decay");
-  if (n_tensors == 0 || total_chunks == 0) return 0;
+  MT_CHECK_TABLE("mt_lamb_stage1_norms");
+  if (n_tensors == 0) return 0;
+  if (total_chunks == 0) {   // every tensor empty: no chunk leaves a partial, both norms of every tensor are 0 (as dle_mt_l2norm answers)
+    hipError_t e = hipMemsetAsync(param_norm, 0, 4 * (size_t)n_tensors, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(update_norm, 0, 4 * (size_t)n_tensors, stream);
+    return e == hipSuccess ? 0 : (int)e;
+  }
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
   float* pp = partial;
   float* pu = partial + total_chunks;
@@ -696,7 +721,8 @@ extern "C" int dle_mt_lamb_stage2(const int64_t* table_dev, int n_tensors, int64
                                   const float* update_norm, const float* lr_dev, float weight_decay, int use_nvlamb,
                                   hipStream_t stream) {
   DLE_CHECK_ARG(copy_dtype >= -1 && copy_dtype <= DLE_BF16, "mt_lamb_stage2: bad copy dtype %d", copy_dtype);
-  DLE_CHECK_ARG(table_dev && param_norm && update_norm && lr_dev, "mt_lamb_stage2: null pointer");
+  DLE_CHECK_ARG(table_dev && lr_dev && ((param_norm && update_norm) || n_tensors == 0), "mt_lamb_stage2: null pointer");
+  MT_CHECK_TABLE("mt_lamb_stage2");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
 #define GO2(GT, CT) hipLaunchKernelGGL((mt_lamb_stage2<GT, CT>), grid, block, 0, stream, (const long long*)table_dev, n_tensors, chunk, noop_flag, param_norm, update_norm, lr_dev, weight_decay, use_nvlamb)
@@ -717,6 +743,7 @@ extern "C" int dle_mt_sgd(const int64_t* table_dev, int n_tensors, int64_t total
                           const float* inv_scale_dev, int copy_dtype, hipStream_t stream) {
   DLE_CHECK_ARG(table_dev, "mt_sgd: null table");
   DLE_CHECK_ARG(copy_dtype == -1 || copy_dtype == DLE_F16 || copy_dtype == DLE_BF16, "mt_sgd: bad copy dtype %d", copy_dtype);
+  MT_CHECK_TABLE("mt_sgd");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
 #define GO3(GT, HM, CT) hipLaunchKernelGGL((mt_sgd<GT, HM, CT>), grid, block, 0, stream, (const long long*)table_dev, n_tensors, chunk, skip_flag_dev, lr_dev, lr_host, momentum, dampening, weight_decay, nesterov, first_step, inv_scale_dev)
@@ -736,6 +763,7 @@ extern "C" int dle_mt_adam(const int64_t* table_dev, int n_tensors, int64_t tota
                            float eps, float weight_decay, const int* step_dev, const float* inv_scale_dev,
                            const float* grad_norm_dev, float max_grad_norm, hipStream_t stream) {
   DLE_CHECK_ARG(table_dev && step_dev, "mt_adam: null table / step");
+  MT_CHECK_TABLE("mt_adam");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   hipLaunchKernelGGL(mt_adam, dim3((unsigned)total_chunks), dim3(MT_BLOCK), 0, stream, (const long long*)table_dev, n_tensors,
                      chunk, skip_flag_dev, lr_dev, lr_host, beta1, beta2, eps, weight_decay, step_dev, inv_scale_dev,
@@ -749,6 +777,7 @@ extern "C" int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t
                                 const int* step_dev, const float* inv_scale_dev, const float* tensor_mul_dev, hipStream_t stream) {
   DLE_CHECK_ARG(table_dev && step_dev, "mt_adam_copy: null table / step");
   DLE_CHECK_ARG(copy_dtype == -1 || copy_dtype == DLE_F16 || copy_dtype == DLE_BF16, "mt_adam_copy: bad copy dtype %d", copy_dtype);
+  MT_CHECK_TABLE("mt_adam_copy");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   dim3 grid((unsigned)total_chunks), block(MT_BLOCK);
 #define GO(CT) hipLaunchKernelGGL(mt_adam_copy<CT>, grid, block, 0, stream, (const long long*)table_dev, n_tensors, chunk, skip_flag_dev, lr_dev, lr_host, beta1, beta2, eps, step_dev, inv_scale_dev, tensor_mul_dev)
@@ -763,7 +792,7 @@ extern "C" int dle_mt_adam_copy(const int64_t* table_dev, int n_tensors, int64_t
 extern "C" int dle_mt_ema(const int64_t* table_dev, int n_tensors, int64_t total_chunks, int chunk, const float* coef_dev,
                           float mu_host, float one_minus_mu_host, hipStream_t stream) {
   DLE_CHECK_ARG(table_dev, "mt_ema: null table");
-  DLE_CHECK_ARG(chunk > 0 && chunk % 4 == 0, "mt_ema: chunk must be a positive multiple of 4");
+  MT_CHECK_TABLE("mt_ema");
   if (n_tensors == 0 || total_chunks == 0) return 0;
   hipLaunchKernelGGL(mt_ema, dim3((unsigned)total_chunks), dim3(MT_BLOCK), 0, stream, (const long long*)table_dev, n_tensors,
                      chunk, coef_dev, mu_host, one_minus_mu_host);

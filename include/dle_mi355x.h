@@ -219,7 +219,11 @@ int dle_colsum_batched(const int64_t* table_dev, int n, int64_t M, int N, int64_
  * torch.optim.SGD, Classification/ConvNets/image_classification/optimizers.py:34-56).
  * Tensor lists are described by a device-resident int64 table:
  *   { size[n] | chunk_start[n+1] | ptr[list 0][n] | ptr[list 1][n] | ... }
- * built on the host with dle_mt_table_fill and copied to the device once per address set.      */
+ * built on the host with dle_mt_table_fill and copied to the device once per address set.
+ * The table rule, checked by every dle_mt_* entry point below and by dle_mt_adam / dle_mt_adam_copy / dle_mt_ema before anything
+ * is launched (-1, message in dle_last_error()): chunk > 0 and chunk % 4 == 0; 0 <= total_chunks <= INT_MAX, total_chunks being
+ * chunk_start[n] of a table filled with the same chunk.  Zero-length tensors are legal (chunk_start[t] == chunk_start[t + 1]);
+ * n_tensors == 0 or total_chunks == 0 launches nothing, and the norm outputs of such a call are zeros.                        */
 int64_t dle_mt_table_len(int n_tensors, int n_lists);
 int64_t dle_mt_table_fill(int64_t* table_host, int n_tensors, int n_lists, const int64_t* sizes,
                           const void* const* ptrs, int chunk);
