@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void dot_bwd_mfma(const unsigned short* __rest
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int t = lane + 64 * it;
-      tv[it] = ub[C + (t < ntril ? t : 0)];
+      tv[it] = ub[t < ntril ? C + t : 0];              // (clamped to the row's head: with R = 1 and OW == C, ub[C] is the next row)
     }
     mv = *(const ushort8_t*)(ub + (lane * 8 < C ? lane * 8 : 0));
   };
@@ -444,7 +444,13 @@ extern "C" int dle_dot_interact_bwd_checked(const void* x, const void* upstream,
   const bool fast = !force_generic && dtype != DLE_F32 && rows <= 32 && (cols == 32 || cols == 64 || cols == 128 || cols == 256) &&
                     aligned16(x) && aligned16(upstream) && aligned16(grad) && aligned16(mlp_grad);   /* NULL is aligned */
   if (fast) {
+    // four wavefront slices: 27,136 bytes at C = 32 ... 79,872 at C = 256.  (Past 64 KB: the runtime takes a plain launch of the
+    // NB = 8 instantiation on gfx950 -- observed, and pinned bit for bit by tests/test_gpu_dlrm_reference.py; the device's own
+    // limit is checked here.)
     const size_t lds = (size_t)4 * (32 * (cols + 8) + 32 * DOT_BWD_USTRIDE + 256) * 2;
+    const DleDeviceLimits* lim = dle_device_limits();
+    DLE_CHECK_ARG(lim && lds <= (size_t)lim->lds_per_block, "dot_interact_bwd: %zu bytes of LDS for %d columns, the device has %d",
+                  lds, cols, lim ? lim->lds_per_block : 0);
     // persistent: two workgroups per CU (180 registers at C = 128), each wavefront walks its samples
     const int per_cu = 2;
     int nblk = (batch + 3) / 4;

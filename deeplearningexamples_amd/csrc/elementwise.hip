@@ -138,8 +138,11 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const void* __restrict_
     const float e = __expf(-ax);
     acc += fmaxf(x, 0.f) - x * y + log1pf(e);
     if (dlogits) {
-      const float s = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-      StF<DT>::st(dlogits, i, (s - y) * gs);
+      // sigmoid(x) - y as (1 - y) sigmoid(x) - y sigmoid(-x): both sigmoids are quotients of e, so a label of 0 or 1 selects one of
+      // them exactly, where 1 / (1 + e) - 1 had lost log2(1 / e) bits (x = 8, y = 1: 11 of the 24)
+      const float p = 1.f / (1.f + e), q = e / (1.f + e);
+      const float s = x >= 0.f ? p : q, c = x >= 0.f ? q : p;
+      StF<DT>::st(dlogits, i, ((1.f - y) * s - y * c) * gs);
     }
   }
   acc = block_sum(acc, red);
