@@ -926,8 +926,12 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const unsigned short* 
     const int n = (int)(t / P);
     float best[8];
     unsigned char bi[8];
+    // the scan starts from the window's first tap INSIDE the image (ATen: maxindex = the first pixel, maxval = -inf): a window
+    // that holds only -inf names that pixel, not the padding tap 0, whose gradient the backward pass would drop
+    const int r_in = p * st < pad ? pad - p * st : 0, s_in = q * st < pad ? pad - q * st : 0;
+    const unsigned char first = (unsigned char)(r_in * ks + s_in);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; bi[k] = 0; }
+    for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; bi[k] = first; }
     for (int r = 0; r < ks; ++r) {
       const int h = p * st - pad + r;
       if (h < 0 || h >= H) continue;
@@ -1313,6 +1317,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_k3s2_kernel(const unsigne
       }
     float best[8];
     unsigned bi[8];
+    // (code 0 as the start: maxpool_fwd_kernel's "first tap inside the image" matters only for a window of -inf, and the values
+    //  scanned here are >= 0 or NaN after the ReLU, so the first tap inside always replaces it)
 #pragma unroll
     for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; bi[k] = 0; }
 #pragma unroll
