@@ -34,6 +34,7 @@ _SIGS = {
                                      c_int, c_void_p]),
     "dle_dot_interact_bwd_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_void_p, c_void_p]),
+    "dle_dlrm_gather_interact_try": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_void_p]),
     "dle_emb_gather_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int,
                                    c_int, c_i64, c_void_p]),
     "dle_emb_offset_indices": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),

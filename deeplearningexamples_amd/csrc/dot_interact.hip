@@ -484,3 +484,167 @@ extern "C" int dle_dot_interact_bwd(const void* x, const void* upstream, void* g
                                     hipStream_t stream) {
   return dle_dot_interact_bwd_checked(x, upstream, grad, mlp_grad, batch, rows, cols, dtype, force_generic, nullptr, stream);
 }
+
+// ------------------------------------------------------------------ inference: embedding gather fused into the forward
+// X is never materialised: lane (row, h) of dot_fwd_mfma_walk takes its 16-byte pieces from the 16-bit joint table at the row the
+// index tensor names (rows 1..T) or from the bottom-MLP output (row 0).  The MFMA sequence, the accumulation order and the assembly
+// of the output row are those of dot_fwd_mfma / dot_fwd_mfma_walk, so the result has the bits of dle_dot_interact_fwd over
+// cat(mlp_out, table16[rows]).  Per sample at 26 x 128: 27 x 256 B of rows + 208 B of ids in, 960 B out (the training forward's
+// fp32 gather + 16-bit X write + X read-back + output: ~27.8 KB).
+// joint row of a lookup: the int64 arithmetic of emb_gather_fwd (python floor-mod, then + offsets[t])
+__device__ __forceinline__ long long gi_joint_row(long long ix, long long m, long long off, bool hashed) {
+  if (hashed) {
+    ix %= m;
+    if (ix < 0) ix += m;
+  }
+  return ix + off;
+}
+
+// Persistent form (C = 16 NK): the walk of dot_fwd_mfma_walk with ONE more stage in front -- the ids of a sample are a dependent
+// HBM round trip ahead of its rows, so they are requested two samples ahead (a register per lane), the rows one sample ahead.
+template <int DT, int NK>
+__global__ __launch_bounds__(256) void gather_interact_walk(const unsigned short* __restrict__ table, const long long* __restrict__ indices,
+                                                            const long long* __restrict__ offsets, const long long* __restrict__ hash_sizes,
+                                                            const unsigned short* __restrict__ mlp, unsigned short* __restrict__ out,
+                                                            long long B, int T, int OW) {
+  constexpr int C = 16 * NK;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned short* so = (unsigned short*)smem_raw + (size_t)wave * OW;
+  const int row = lane & 31, h = lane >> 5;
+  const int R = T + 1;
+  const long long nwaves = (long long)gridDim.x * 4;
+  const bool live = row < R;
+  const bool emb = row >= 1 && row < R;                    // this lane's row comes from the table
+  const int t = emb ? row - 1 : 0;                          // (clamped: every load below is unconditional, masked at use)
+  const bool hashed = hash_sizes != nullptr;
+  const long long hm = hashed ? hash_sizes[t] : 1, off = offsets ? offsets[t] : 0;
+  const int ntril = R * (R - 1) / 2;
+  ushort8_t xv[NK];
+  auto issue = [&](long long b, long long ix) __attribute__((always_inline)) {
+    const unsigned short* xr = (emb ? table + gi_joint_row(ix, hm, off, hashed) * (long long)C : mlp + b * (long long)C) + h * 8;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) xv[k] = *(const ushort8_t*)(xr + k * 16);
+  };
+  long long b = (long long)blockIdx.x * 4 + wave;
+  long long ix = 0;                                         // raw id of this lane's row, one sample ahead of xv
+  if (b < B) {
+    issue(b, indices[b * T + t]);
+    if (b + nwaves < B) ix = indices[(b + nwaves) * T + t];
+  }
+  for (; b < B; b += nwaves) {
+    ushort8_t cur[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) cur[k] = live ? xv[k] : (ushort8_t){0, 0, 0, 0, 0, 0, 0, 0};
+    if (b + nwaves < B) issue(b + nwaves, ix);
+    if (b + 2 * nwaves < B) ix = indices[(b + 2 * nwaves) * T + t];
+    float16_t acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      acc = Mfma32<DT>::run(cur[k], cur[k], acc);
+      if (row == 0) *(ushort8_t*)(so + k * 16 + h * 8) = cur[k];   // bottom-MLP slice = row 0 of X
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int j = row;
+      if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
+    }
+    for (int p = C + ntril + lane; p < OW; p += 64) so[p] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // (lanes exchange data through `so`: see dot_fwd_mfma_walk)
+    unsigned short* o = out + (size_t)b * OW;
+    for (int q = lane * 8; q < OW; q += 512) *(ushort8_t*)(o + q) = *(const ushort8_t*)(so + q);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // ... and before the next sample's writes
+  }
+}
+
+// One-shot form for the other widths (C % 16 == 0): dot_fwd_mfma with the gathered addresses.
+template <int DT>
+__global__ __launch_bounds__(256) void gather_interact_any(const unsigned short* __restrict__ table, const long long* __restrict__ indices,
+                                                           const long long* __restrict__ offsets, const long long* __restrict__ hash_sizes,
+                                                           const unsigned short* __restrict__ mlp, unsigned short* __restrict__ out,
+                                                           long long B, int T, int C, int OW) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + wave;
+  unsigned short* so = (unsigned short*)smem_raw + (size_t)wave * OW;
+  const int row = lane & 31, h = lane >> 5;
+  const int R = T + 1;
+  if (b < B) {
+    const bool live = row < R, emb = row >= 1 && row < R;
+    const int t = emb ? row - 1 : 0;
+    const bool hashed = hash_sizes != nullptr;
+    const long long jr = gi_joint_row(indices[b * T + t], hashed ? hash_sizes[t] : 1, offsets ? offsets[t] : 0, hashed);
+    const unsigned short* xr = (emb ? table + jr * (long long)C : mlp + b * (long long)C) + h * 8;
+    float16_t acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < C; k0 += 16) {
+      ushort8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (live) v = *(const ushort8_t*)(xr + k0);
+      acc = Mfma32<DT>::run(v, v, acc);
+      if (row == 0) *(ushort8_t*)(so + k0 + h * 8) = v;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int j = row;
+      if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
+    }
+    const int ntril = R * (R - 1) / 2;
+    for (int p = C + ntril + lane; p < OW; p += 64) so[p] = 0;
+  }
+  __syncthreads();
+  if (b < B) {
+    unsigned short* o = out + (size_t)b * OW;
+    for (int q = lane * 8; q < OW; q += 512) *(ushort8_t*)(o + q) = *(const ushort8_t*)(so + q);
+  }
+}
+
+// 1: launched, 0: outside the envelope (nothing launched, nothing written), anything else: error (the *_try convention)
+extern "C" int dle_dlrm_gather_interact_try(const void* table16, const int64_t* indices, const int64_t* offsets,
+                                            const int64_t* hash_sizes, const void* mlp_out, void* out, int64_t batch,
+                                            int tables, int dim, int dtype, hipStream_t stream) {
+  DLE_CHECK_ARG(batch >= 0 && tables >= 1 && dim >= 1, "dlrm_gather_interact: bad shape %lld %d %d", (long long)batch, tables, dim);
+  DLE_CHECK_ARG(dtype == DLE_F32 || dtype == DLE_F16 || dtype == DLE_BF16, "dlrm_gather_interact: bad dtype %d", dtype);
+  if (batch == 0) return 1;   // empty batch: pointers may legitimately be null
+  DLE_CHECK_ARG(table16 && indices && mlp_out && out, "dlrm_gather_interact: null pointer");
+  if (dtype == DLE_F32 || tables + 1 > 32 || (dim % 16) != 0 || !aligned16(table16) || !aligned16(mlp_out) || !aligned16(out)) return 0;
+  const int OW = out_width(tables + 1, dim);
+  const size_t lds = (size_t)4 * OW * 2;
+  if (lds > 64 * 1024 || batch > 0x7fffffffLL * 4) return 0;
+  const long long nblk = (batch + 3) / 4;
+  const dim3 block(256);
+  const long long* ix = (const long long*)indices;
+  const long long* of = (const long long*)offsets;
+  const long long* hs = (const long long*)hash_sizes;
+  if (dim == 16 || dim == 32 || dim == 64 || dim == 128) {
+    // the walk's launch rule (dle_dot_interact_fwd): two workgroups per CU of 256, four samples per workgroup and lap
+    const int per_cu = 2;
+    const dim3 grid((unsigned)(nblk < 256 * per_cu ? nblk : 256 * per_cu));
+#define GO(DT, NK) hipLaunchKernelGGL((gather_interact_walk<DT, NK>), grid, block, lds, stream, (const unsigned short*)table16, ix, of, hs, \
+                                      (const unsigned short*)mlp_out, (unsigned short*)out, (long long)batch, tables, OW)
+#define PICK(DT) do { if (dim == 16) GO(DT, 1); else if (dim == 32) GO(DT, 2); else if (dim == 64) GO(DT, 4); else GO(DT, 8); } while (0)
+    if (dtype == DLE_F16) PICK(DLE_F16); else PICK(DLE_BF16);
+#undef GO
+#undef PICK
+  } else {
+    const dim3 grid((unsigned)nblk);
+    if (dtype == DLE_F16)
+      hipLaunchKernelGGL(gather_interact_any<DLE_F16>, grid, block, lds, stream, (const unsigned short*)table16, ix, of, hs,
+                         (const unsigned short*)mlp_out, (unsigned short*)out, (long long)batch, tables, dim, OW);
+    else
+      hipLaunchKernelGGL(gather_interact_any<DLE_BF16>, grid, block, lds, stream, (const unsigned short*)table16, ix, of, hs,
+                         (const unsigned short*)mlp_out, (unsigned short*)out, (long long)batch, tables, dim, OW);
+  }
+  {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      dle_set_error("dlrm_gather_interact launch failed: %s", hipGetErrorString(e));
+      return (int)e + 1000;
+    }
+  }
+  return 1;
+}

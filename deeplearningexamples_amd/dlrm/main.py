@@ -111,8 +111,6 @@ def build_parser():
 
 def parse_flags(argv=None):
     f = build_parser().parse_args(argv)
-    if f.mode == "inference_benchmark":
-        raise SystemExit("--mode inference_benchmark: inference is outside this path (the train step and its validation pass)")
     if (f.Adam_embedding_optimizer or f.Adam_MLP_optimizer) and f.embedding_sharding == "row":
         raise SystemExit("--Adam_embedding_optimizer / --Adam_MLP_optimizer: Adam runs on the table-wise placement only "
                          "(--embedding_sharding table); the row-sharded trainer implements SGD")
@@ -127,6 +125,8 @@ def parse_flags(argv=None):
 def main(argv=None):
     flags = parse_flags(argv)
     rank, world, local = init_from_env()
+    if flags.mode == "inference_benchmark" and world > 1:           # scripts/main.py:515-516
+        raise ValueError("Inference benchmark only supports singleGPU mode.")
     device = torch.device("cuda", local)
     torch.manual_seed(flags.seed)
     # load_feature_spec (scripts/main.py:183-190): table cardinalities AND the number of numerical features come from the spec
@@ -161,6 +161,8 @@ def main(argv=None):
         embedding_device_mapping=mapping["embedding"], world_num_categorical_features=len(sizes),
         embedding_dim=flags.embedding_dim, hash_indices=flags.hash_indices, fp16=flags.amp, device=device,
         world_size=world, bottom_features_ordered=flags.bottom_features_ordered)
+    if flags.mode == "inference_benchmark":
+        return main_inference_benchmark(flags, sizes, mapping, model, device)
     trainer = DlrmTrainer(model, lr=flags.lr, batch_sizes_per_gpu=batch_sizes, vectors_per_gpu=mapping["vectors_per_gpu"],
                           rank=rank, world_size=world, amp=flags.amp, freeze_mlps=flags.freeze_mlps,
                           freeze_embeddings=flags.freeze_embeddings, adam_embeddings=flags.Adam_embedding_optimizer,
@@ -283,6 +285,41 @@ def main(argv=None):
                                          "average_train_throughput": avg, "training_loss": float(moving_loss.item())})
         dllogger.flush()
     return trainer
+
+
+def main_inference_benchmark(flags, sizes, mapping, model, device):
+    """--mode inference_benchmark (scripts/main.py:277-385, 514-542): per batch size a test loader at that size, host-timed
+    copy-in + predict + synchronize over --inference_benchmark_steps batches, the AUC of sigmoid(logits), and ONE record with the
+    mean latency / throughput of every size.  --cuda_graphs: one captured graph per batch size (DlrmPredictor(graphs=True))."""
+    from .infer import DlrmPredictor, benchmark_latencies, summarize_latencies
+    from .utils import roc_auc_score
+    if flags.load_checkpoint_path:               # scripts/main.py:493-495
+        ckpt.make_distributed_checkpoint_loader(mapping, 0, device=device).load_checkpoint(model, flags.load_checkpoint_path)
+    predictor = DlrmPredictor(model, fused=True, graphs=flags.cuda_graphs, release_fp32=True)
+    results = {}
+    for bs in flags.inference_benchmark_batch_sizes:
+        if flags.dataset_type == "parametric":
+            spec = FeatureSpec.from_yaml(os.path.join(flags.dataset, flags.feature_spec))
+            loader = ParametricDataset(spec, "test", batch_size=bs, drop_last_batch=False, numerical_features_enabled=True,
+                                       categorical_features_to_read=spec.get_categorical_feature_names())
+        else:                                    # data/factories.py: the synthetic test set is one fixed batch, repeated
+            g = torch.Generator(device="cpu").manual_seed(flags.seed + 1)
+            loader = SyntheticDataset(flags.synthetic_dataset_num_entries, device="cpu", batch_size=bs,
+                                      numerical_features=flags.synthetic_dataset_numerical_features,
+                                      categorical_feature_sizes=sizes, generator=g)
+
+        def predict(num, cat):                   # the copy-in is inside the timed span, as in the reference
+            return predictor.predict(num.to(device).float(), cat.to(device=device, dtype=torch.int64))
+        latencies, y_true, y_score = benchmark_latencies(predict, loader, flags.inference_benchmark_steps,
+                                                         flags.benchmark_warmup_steps)
+        y_true = torch.cat([t.reshape(-1).float().to(device) for t in y_true])
+        auc = roc_auc_score(y_true, torch.sigmoid(torch.cat(y_score).float()))
+        print("auc: ", auc)
+        results.update(summarize_latencies(latencies, bs))
+    if is_main_process():
+        dllogger.log(step=tuple(), data=results)
+        dllogger.flush()
+    return predictor
 
 
 def main_row_sharded(flags, sizes, rank, world, device):

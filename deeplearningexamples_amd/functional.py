@@ -52,6 +52,38 @@ def dot_interact_bwd(x, upstream, force_generic=False, fuse_mlp_grad=False, grad
     return grad, mlp_grad
 
 
+def gather_interact(table16, indices, offsets, hash_sizes, mlp_out, out=None):
+    """Inference forward of the embedding gather and the dot interaction in one launch: table16 [sum rows, D] 16-bit joint table,
+    indices int64 [B, T], offsets / hash_sizes int64 [T] or None (as emb_gather_fwd), mlp_out [B, D] = row 0 of X ->
+    [B, ceil8((T+1)T/2 + D)], the bits of dot_interact_fwd(cat(mlp_out, table16[rows])).  -> None when the kernel declines (the
+    caller runs the gather and dot_interact_fwd); `out` is not written then."""
+    C.require_cuda(table16, indices, offsets, hash_sizes, mlp_out, out)
+    if table16.dim() != 2 or indices.dim() != 2 or mlp_out.dim() != 2:
+        raise ValueError("gather_interact: table16 [rows, dim], indices [batch, tables], mlp_out [batch, dim]")
+    indices, offsets, hash_sizes = _i64(indices, "indices"), _i64(offsets, "offsets"), _i64(hash_sizes, "hash_sizes")
+    b, t = indices.shape
+    d = table16.shape[1]
+    if tuple(mlp_out.shape) != (b, d) or mlp_out.dtype != table16.dtype:
+        raise ValueError("gather_interact: mlp_out must be [%d, %d] %s" % (b, d, table16.dtype))
+    if not (table16.is_contiguous() and mlp_out.is_contiguous()):
+        raise ValueError("gather_interact: table16 and mlp_out must be contiguous")
+    for name, v in (("offsets", offsets), ("hash_sizes", hash_sizes)):
+        if v is not None and v.numel() < t:
+            raise ValueError("%s has %d entries for %d tables" % (name, v.numel(), t))
+    ow = dot_interact_out_width(t + 1, d)
+    if out is None:
+        out = torch.empty((b, ow), dtype=table16.dtype, device=table16.device)
+    elif tuple(out.shape) != (b, ow) or out.dtype != table16.dtype or not out.is_contiguous():
+        raise ValueError("gather_interact: out must be a contiguous [%d, %d] %s" % (b, ow, table16.dtype))
+    C.annotate(bytes=float(b) * ((t + 1) * d * table16.element_size() + t * 8 + ow * out.element_size()))
+    rc = _timed_optional("dle_dlrm_gather_interact_try", C.lib().dle_dlrm_gather_interact_try,
+                         (C.ptr(table16), C.ptr(indices), C.ptr(offsets), C.ptr(hash_sizes), C.ptr(mlp_out), C.ptr(out), b, t, d,
+                          C.dt(table16), C.stream()))
+    if rc not in (0, 1):
+        C.check(rc - 1000 if rc > 1000 else -1, "dle_dlrm_gather_interact_try")
+    return out if rc == 1 else None
+
+
 # ------------------------------------------------------------------ DLRM embeddings
 def _i64(t, name):
     if t is None:

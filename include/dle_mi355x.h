@@ -55,6 +55,19 @@ int dle_dot_interact_bwd_checked(const void* x, const void* upstream, void* grad
                                  int batch, int rows, int cols, int dtype, int force_generic,
                                  float* found_inf, hipStream_t stream);
 
+/* Inference: the embedding gather fused into the interaction forward (X is never materialised).  Replaces
+ * FusedJointEmbedding + dotBasedInteractFwd under model.half()
+ *   Recommendation/DLRM/dlrm/nn/embeddings.py:163-224, dlrm/nn/interactions.py:85-101, dlrm/scripts/main.py:520-522
+ * table16: 16-bit joint table [sum rows, dim] (dtype DLE_F16 / DLE_BF16); indices int64 [batch, tables]; offsets / hash_sizes as
+ * for dle_emb_gather_fwd (NULL: joint ids / no hashing; same int64 arithmetic); mlp_out [batch, dim] 16-bit = row 0 of X;
+ * out [batch, OW], OW = dle_dot_interact_out_width(tables + 1, dim): [mlp_out | strict lower tri of X X^T | 0 pad], bit-identical
+ * to dle_dot_interact_fwd over cat(mlp_out, table16[rows]).  Envelope: tables + 1 <= 32, dim % 16 == 0, 16-bit dtype, 16-byte
+ * aligned table16 / mlp_out / out.
+ * 1: launched, 0: outside the envelope (caller takes gather + dle_dot_interact_fwd), > 1 or -1: error */
+int dle_dlrm_gather_interact_try(const void* table16, const int64_t* indices, const int64_t* offsets,
+                                 const int64_t* hash_sizes, const void* mlp_out, void* out,
+                                 int64_t batch, int tables, int dim, int dtype, hipStream_t stream);
+
 /* ---- DLRM embeddings --------------------------------------------------------------------------
  * replaces dlrm.cuda_ext.fused_embedding.gather_gpu_fused_fwd / _bwd
  *   Recommendation/DLRM/dlrm/cuda_src/pytorch_embedding_ops.cpp:3-21, gather_gpu_fused.cu:107-220
