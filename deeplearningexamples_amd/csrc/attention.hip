@@ -37,7 +37,7 @@ struct AttnArgs {
   const float* mask_add;        // [B, S] additive mask (0 / -10000) or NULL
   unsigned short* ctx;          // [T, H]   (forward out)
   unsigned short* dqkv;         // [T, 3H]  (backward out)
-  float* stats;                 // [B * heads, S, 2]: row max of the scaled+masked scores, 1 / sum of exp
+  float* stats;                 // [B * heads, S, sw]: row max of the scaled+masked scores, 1 / sum of exp (sw = 2 at S = 128, else 4)
   unsigned char* mask_out;      // optional bit-packed keep mask [B * heads * S * S / 8], forward only
   const unsigned char* mask_in; // optional (backward, S = 128): the keep mask the forward pass wrote -- read instead of re-drawn
   float* colsum;                // optional (backward): [B, 3H] column sums of this sequence's rows of dqkv (QKV bias gradient partials)
@@ -871,8 +871,10 @@ static int attn_check(const char* what, int B, int S, int heads, int head_dim, i
 }
 
 // context[T, H] = dropout(softmax(q k^T * scale + mask_add)) v per (sequence, head); qkv [T = B*S, 3H] as written by the
-// fused QKV projection.  stats [B*heads, S, 2] fp32 receives (row max, 1 / row sum) for the backward pass; keep_mask
-// (optional, B*heads*S*S/8 bytes) receives the dropout keep bits in the layout of dle_softmax_dropout_fwd.
+// fused QKV projection.  stats [B*heads, S, W] fp32, W = dle_attention_stats_floats(S) (2 at S = 128, 4 for S > 128), receives
+// (row max, 1 / row sum) in words 0, 1 of every row for the backward pass; for S > 128 the backward pass writes the row's delta
+// into word 2 and word 3 is never touched.  keep_mask (optional, B*heads*S*S/8 bytes) receives the dropout keep bits in the
+// layout of dle_softmax_dropout_fwd.
 extern "C" int dle_attention_fwd(const void* qkv, const float* mask_add, void* ctx, float* stats, void* keep_mask, int B,
                                  int S, int heads, int head_dim, float scale, float p, uint64_t seed, uint64_t offset,
                                  const uint64_t* offset_base, int dtype, hipStream_t stream) {

@@ -575,8 +575,9 @@ int dle_conv2d_dgrad_s2(const void* dy, const void* w, void* dx, int N, int H, i
  * BertSelfAttention.forward between the QKV and the output projection, LanguageModeling/BERT/modeling.py:340-384 (torch.bmm +
  * softmax + nn.Dropout + torch.bmm) and its autograd backward.  qkv [T = B*S, 3H] (q | k | v, head h at columns h*64 of each
  * third), ctx / dctx [T, H], dqkv [T, 3H]; mask_add fp32 [B, S] (0 / -10000) or NULL; stats fp32 [B*heads, S, W] with
- * W = dle_attention_stats_floats(S): (row max, 1 / row sum) saved for backward (+ for S > 128 a third word the backward pass
- * uses as scratch: the row's delta); keep_mask (optional, B*heads*S*S/8 bytes) = the dropout keep bits in the layout of
+ * W = dle_attention_stats_floats(S), 2 at S = 128 and 4 for S > 128 (never [B*heads, S, 2] there): words 0, 1 of a row are
+ * (row max, 1 / row sum) saved for backward; for S > 128 word 2 is scratch of the backward pass (the row's delta) and word 3 is
+ * unused; keep_mask (optional, B*heads*S*S/8 bytes) = the dropout keep bits in the layout of
  * dle_softmax_dropout_fwd.  The backward regenerates probabilities and mask from (qkv, stats, seed, offset): nothing of shape
  * [B, heads, S, S] is stored -- for S > 128 K / V are streamed through LDS in 128-key blocks (forward: online max / sum, then a
  * second pass with the final statistics; backward: a per-query-block kernel for delta and dQ, a per-key-block kernel for dK / dV).
