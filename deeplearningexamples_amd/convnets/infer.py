@@ -1,0 +1,174 @@
+"""ResNet-50 inference on the gfx950 library: images -> logits / top-k, the forward the reference serves from classify.py and
+main.py --evaluate (Classification/ConvNets/classify.py:119-144, image_classification/training.py:98-105 under model.eval()).
+
+ResNetTrainer.infer (the validation pass of training) needs a whole trainer and runs every conv + BatchNorm unit as two launches:
+the convolution writes a 16-bit t, dle_bn_fwd_apply reads it (and the residual) back.  In evaluation mode BatchNorm is a
+per-channel affine map with constant coefficients, so here it sits in the convolution's epilogue, on the fp32 accumulator
+(functional.conv2d_fwd_affine): one launch per unit, the activation written once and rounded once.  The weights are the
+training path's 16-bit KRSC copies, unmodified -- the coefficients stay fp32 (a folded 16-bit weight would overflow where
+running_var is tiny).
+
+One stream: image layout pass -> stem convolution -> affine + ReLU + max pooling -> 52 fused units (conv1, conv2: affine + ReLU;
+downsample: affine; conv3: affine + residual + ReLU) -> average pooling -> fc.  graphs=True keeps one captured graph (a single
+chain) and one static input buffer per input shape; the logits of a call then live in a buffer the classifier owns: copy them
+before the next call at that shape.
+"""
+import torch
+
+from .. import functional as F
+from ..utils.graph import GraphedStep
+from .resnet import ResNet50
+
+# Units routed back to the two-launch form (convolution, then the stand-alone BatchNorm-apply): (kernel size, stride, C, Ko).
+# The place to put a unit whose fused launch measures slower than the pair; tools/rn50_infer_perf.py times whole networks only, so
+# no unit has been measured on its own and none is listed (DESIGN.md section 4h has the whole-network table).
+TWO_LAUNCH_UNITS = frozenset()
+
+
+def fold_bn(gamma, beta, running_mean, running_var, eps):
+    """Evaluation-mode BatchNorm as y = scale * x + shift, in fp32: scale = gamma * rsqrt(running_var + eps),
+    shift = beta - running_mean * scale."""
+    scale = gamma.float() * torch.rsqrt(running_var.float() + eps)
+    shift = beta.float() - running_mean.float() * scale
+    return scale.contiguous(), shift.contiguous()
+
+
+def state_from_checkpoint(obj, ema=False):
+    """The model's state dict out of what torch.load returned: the trainer's checkpoint_*.pth.tar (`state_dict`, or the averaged
+    model `state_dict_ema` with ema=True), or a bare state dict; `module.` prefixes (DistributedDataParallel) are stripped."""
+    if not isinstance(obj, dict):
+        raise ValueError("not a checkpoint: expected a dict, got %s" % type(obj).__name__)
+    if ema:
+        keys = [k for k in ("state_dict_ema", "ema_state_dict") if k in obj]
+        if not keys:
+            raise ValueError("this checkpoint holds no averaged model (state_dict_ema): it was not trained with --use-ema")
+        state = obj[keys[0]]
+    else:
+        state = obj.get("state_dict", obj)
+    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+
+
+def affine_relu_maxpool(t, scale, shift, zeros, ones):
+    """maxpool3x3/2/pad1(relu(scale[c] * t + shift[c])) of the stem's 16-bit NHWC convolution output in one pass (H, W even):
+    dle_bn_relu_maxpool_fwd, the training forward's kernel, with (mean, rstd, gamma, beta) = (zeros, scale, ones, shift) -- it forms
+    rstd * gamma = scale and beta - mean * scale = shift exactly.  zeros / ones: constant fp32 [C] tensors the caller keeps (nothing
+    is filled per call).  (The kernel also writes the argmax and keep bits training needs.)"""
+    return F.bn_relu_maxpool_fwd(t, zeros, scale, ones, shift)[0]
+
+
+class _Unit:
+    """One conv + BatchNorm unit as the kernels read it: the 16-bit KRSC weight and the fp32 affine coefficients."""
+    __slots__ = ("w16", "scale", "shift", "stride", "pad", "relu", "two_launch", "ones", "zeros")
+
+
+class ResNet50Classifier:
+    def __init__(self, model, dtype=torch.bfloat16, device=None, graphs=False):
+        """model: a ResNet50 (left untouched; nothing of it is referenced afterwards) or its state dict (any device; `module.`
+        prefixes allowed).  dtype: torch.float16 or torch.bfloat16.  graphs: replay one captured graph per input shape."""
+        if dtype == torch.float32:
+            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
+                             "recipes are not built)")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("ResNet50Classifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        if not isinstance(model, ResNet50):
+            state = state_from_checkpoint(model)
+            dev = torch.device(device if device is not None else "cuda")
+            module = ResNet50(num_classes=state["fc.weight"].shape[0], device=dev)
+            module.load_state_dict(state)
+            model = module
+        self.dev = model.fc.weight.device
+        self.dtype, self.graphs = dtype, bool(graphs)
+        self.num_classes = model.fc.weight.shape[0]
+        stem, blocks = model.units()
+        with torch.no_grad():
+            self.stem = self._unit(stem)
+            self.stem_w2 = F.stem_pack_weight(model.conv1.weight.data, dtype)
+            self.blocks = [tuple(self._unit(u) if u is not None else None for u in blk) for blk in blocks]
+            self.fc_w16 = F.cast(model.fc.weight.data, dtype)
+            self.fc_bias = model.fc.bias.data.float().clone()
+        self._mean_std = None
+        self._graphs = {}                     # (input shape, input dtype) -> GraphedStep
+
+    def _unit(self, u):
+        w = u.conv.weight.data
+        ko, ci, r, s = w.shape
+        cp = (ci + 7) // 8 * 8                # (the stem's 3 channels, padded for the generic convolution route)
+        o = _Unit()
+        o.w16 = torch.zeros((ko, r, s, cp), dtype=self.dtype, device=self.dev)
+        F.cast_rows(w.permute(0, 2, 3, 1).reshape(ko * r * s, ci), self.dtype, cols_out=cp, out=o.w16.view(ko * r * s, cp))
+        o.scale, o.shift = fold_bn(u.bn.weight.data, u.bn.bias.data, u.bn.running_mean, u.bn.running_var, u.bn.eps)
+        o.stride, o.pad, o.relu = u.stride, u.pad, u.relu
+        o.two_launch = (u.k, u.stride, ci, ko) in TWO_LAUNCH_UNITS
+        # what the kernels of the training forward take as (mean, rstd, gamma, beta): (0, scale, 1, shift) -- the stem's pooling pass
+        # (affine_relu_maxpool) and the stand-alone apply of a two-launch unit
+        o.ones, o.zeros = torch.ones_like(o.scale), torch.zeros_like(o.scale)
+        return o
+
+    @classmethod
+    def from_checkpoint(cls, path, ema=False, **kw):
+        """path: the trainer's checkpoint_*.pth.tar (ema=True: its averaged model), the file checkpoint2model writes, or any
+        saved state dict."""
+        obj = torch.load(path, map_location="cpu", weights_only=False)
+        return cls(state_from_checkpoint(obj, ema=ema), **kw)
+
+    # ------------------------------------------------------------------ the chain
+    def _run(self, u, x, residual=None):
+        if u.two_launch:
+            t = F.conv2d_fwd(x, u.w16, u.stride, u.pad)
+            return F.bn_fwd_apply(t, u.zeros, u.scale, u.ones, u.shift, residual=residual, relu=u.relu, want_mask=False)[0]
+        return F.conv2d_fwd_affine(x, u.w16, u.scale, u.shift, u.stride, u.pad, residual=residual, relu=u.relu)
+
+    def _stem(self, images):
+        """-> the pooled 16-bit NHWC activation [N, H/4, W/4, 64]."""
+        h, w = images.shape[-2:]
+        p, q = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        stem4 = w <= 224 and p % 2 == 0 and q % 2 == 0
+        cp = 4 if stem4 else 8
+        if images.dtype == torch.uint8:
+            if self._mean_std is None:
+                from .dataloaders import IMAGENET_MEAN, IMAGENET_STD
+                self._mean_std = (torch.tensor(IMAGENET_MEAN, device=self.dev) * 255.0, torch.tensor(IMAGENET_STD, device=self.dev) * 255.0)
+            x = F.u8_nchw_normalize_nhwc(images, self._mean_std[0], self._mean_std[1], self.dtype, cp)
+        else:
+            x = F.nchw_to_nhwc(images, self.dtype, cp)
+        u = self.stem
+        if stem4:
+            # the stem's own kernel without statistics, then affine + ReLU + 3x3/2 max pooling in one pass: the 112x112x64
+            # activation is written once
+            t = F.stem_conv_fwd(x, self.stem_w2, want_stats=False)[0]
+            return affine_relu_maxpool(t, u.scale, u.shift, u.zeros, u.ones)
+        # images wider than 224 pixels / odd stem output: the generic convolution on the 8-channel image, then the pooling
+        return F.maxpool_fwd(F.conv2d_fwd_affine(x, u.w16, u.scale, u.shift, 2, 3, relu=True))[0]
+
+    def _forward(self, images):
+        h = self._stem(images)
+        for (u1, u2, u3, ud) in self.blocks:
+            res = self._run(ud, h) if ud is not None else h
+            h = self._run(u3, self._run(u2, self._run(u1, h)), residual=res)
+        pooled = F.avgpool_fwd(h)
+        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
+                      out_dtype=torch.float32, bias=self.fc_bias)
+
+    def logits(self, images):
+        """images: fp32 (or uint8, normalised on the way in) NCHW, contiguous or channels_last -> fp32 logits [N, classes]."""
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError("ResNet50Classifier: images must be [N, 3, H, W] (got %s)" % (tuple(images.shape),))
+        if images.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("ResNet50Classifier: fp32 or uint8 images (got %s)" % images.dtype)
+        if images.device != self.dev:
+            images = images.to(self.dev)
+        if not images.is_contiguous():
+            images = images.contiguous()          # --memory-format nhwc loaders hand over channels_last tensors
+        with torch.no_grad():
+            if not self.graphs:
+                return self._forward(images)
+            key = (tuple(images.shape), images.dtype)
+            g = self._graphs.get(key)
+            if g is None:
+                g = self._graphs[key] = GraphedStep(self._forward, warmup_steps=2)
+            return g(images)
+
+    def predict(self, images, topk=5):
+        """-> (softmax probabilities [N, classes] fp32, the indices [N, topk] of the most probable classes, most probable first)."""
+        probs = torch.softmax(self.logits(images), dim=1)
+        return probs, torch.topk(probs, min(topk, probs.shape[1]), dim=1).indices

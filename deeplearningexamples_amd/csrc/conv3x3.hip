@@ -23,6 +23,9 @@
 //    per CU.  Epilogue: each wavefront transposes its own 32 x NT fp32 block through LDS (no workgroup barrier),
 //    16-byte stores of whole channel rows, padding slots skipped; optional per-tile column sums / sums of squares of
 //    the rounded output for the BatchNorm that follows (same contract as dle_conv2d_fwd_colstats).
+//  * inference (template parameter AFF, forward only): the same body with the evaluation-mode BatchNorm in that epilogue --
+//    y = relu?(fmaf(scale[ko], acc, shift[ko]) + residual) on the fp32 block, one rounding.  Its own instantiations: the training
+//    kernels above keep their registers and their bits.
 #include "gemm_tiles.h"
 
 #define C3_MT 256
@@ -36,9 +39,15 @@ struct C3Args {
   int Wp, IMG, G;              // padded row length, slots per image, total slots
   int tiles_m, tiles_n, pieces;
   FastDiv dIMG, dWp;
+  // the per-channel affine epilogue of the inference instantiations (AFF, dle_conv2d_fwd_affine); unread by the others
+  const float* scale;             // [CO]
+  const float* shift;             // [CO]
+  const unsigned short* residual; // [N, H, W, CO] or NULL
+  int relu;
 };
 
-template <int DT, bool DGRAD, int NT>
+// AFF (forward only): the inference epilogue y = relu?(fmaf(scale[ko], acc, shift[ko]) + residual) instead of the plain store
+template <int DT, bool DGRAD, int NT, bool AFF = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(C3Args p) {
   constexpr int WTN = NT / 32;
   typedef Loader<DGRAD ? 1 : 0, NT, 4> LB;
@@ -162,6 +171,61 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(C3Args p) {
   constexpr int LPR = NT / 8, RPT = 64 / LPR, TRIPS = 32 / RPT, MASK = NT / 4 - 1;
   float* epi = (float*)smem_raw + wave * (32 * NT);
   const int erow = lane / LPR, ecg = lane % LPR;
+  if constexpr (AFF) {
+    // the lane's 8 channels are the same on every trip: their coefficients live in registers.  The residual rows of a 32-pixel
+    // pass (same addresses as the stores, padding slots skipped) are requested BEFORE the block is staged, so they fly under
+    // the LDS transposition.
+    float sc[8], sh[8];
+    {
+      const float4_t s0 = *(const float4_t*)(p.scale + n0 + ecg * 8), s1 = *(const float4_t*)(p.scale + n0 + ecg * 8 + 4);
+      const float4_t h0 = *(const float4_t*)(p.shift + n0 + ecg * 8), h1 = *(const float4_t*)(p.shift + n0 + ecg * 8 + 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { sc[r] = s0[r]; sc[4 + r] = s1[r]; sh[r] = h0[r]; sh[4 + r] = h1[r]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int off[TRIPS];                                      // element offset of the lane's 8 channels of trip t, -1: padding slot
+      ushort8_t rv[TRIPS];
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        const int g = g0 + wave * 64 + i * 32 + t * RPT + erow;
+        const int n = fd_div(g, p.dIMG), rem = g - n * p.IMG;
+        const int hp = fd_div(rem, p.dWp), wp = rem - hp * p.Wp;
+        const bool ok = g < p.G && hp >= 1 && wp >= 1 && wp <= p.W;
+        off[t] = ok ? ((n * p.H + (hp - 1)) * p.W + (wp - 1)) * p.CO + n0 + ecg * 8 : -1;   // (< 2^31 elements: conv_check)
+        rv[t] = (ushort8_t){0, 0, 0, 0, 0, 0, 0, 0};
+        if (p.residual && ok) rv[t] = *(const ushort8_t*)(p.residual + off[t]);
+      }
+#pragma unroll
+      for (int j = 0; j < WTN; ++j)
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+          const float4_t v = {acc[i][j][qd * 4 + 0], acc[i][j][qd * 4 + 1], acc[i][j][qd * 4 + 2], acc[i][j][qd * 4 + 3]};
+          const int c4 = j * 8 + qd * 2 + fh;
+          *(float4_t*)(epi + fr * NT + ((c4 ^ (fr & MASK)) << 2)) = v;
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        const int row = t * RPT + erow;
+        const float4_t lo = *(const float4_t*)(epi + row * NT + (((2 * ecg) ^ (row & MASK)) << 2));
+        const float4_t hi = *(const float4_t*)(epi + row * NT + (((2 * ecg + 1) ^ (row & MASK)) << 2));
+        if (off[t] >= 0) {
+          float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          float rf[8];
+          unpack8<DT>(rv[t], rf);                          // (all zero without a residual)
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            v[r] = __builtin_fmaf(sc[r], v[r], sh[r]) + rf[r];
+            if (p.relu) v[r] = v[r] > 0.f ? v[r] : 0.f;
+          }
+          *(ushort8_t*)(p.y + off[t]) = pack8<DT>(v);
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    return;
+  }
   float st0[8], st1[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) { st0[r] = 0.f; st1[r] = 0.f; }
@@ -244,30 +308,44 @@ extern "C" int dle_conv3x3_tiles(int N, int H, int W) {
   return (int)((G + C3_MT - 1) / C3_MT);
 }
 
+// The envelope of the halo kernel and its launch geometry: false = outside (the caller uses the im2col GEMM).  CI / CO: the
+// channel counts of the tensors the kernel reads / writes.
+static bool c3_plan(const void* x, const void* w, const void* y, int N, int H, int W, int CI, int CO, int dgrad, int dtype, C3Args* out,
+                    int* nt_out, size_t* lds_out) {
+  if (g_conv3x3_mode == 0) return false;
+  if ((CI & 63) || (CO & 63) || (dtype != DLE_F16 && dtype != DLE_BF16)) return false;
+  // 7x7 images: a third of the 256-slot tile is padding and the layer is bound by the weight traffic per tile; the
+  // forward im2col GEMM measured 7 % faster there (tools/kbench/conv_bench), the data gradient 26 % slower
+  if (!dgrad && g_conv3x3_mode < 1 && H * W < 100) return false;
+  if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y)) & 15) return false;
+  const long long Wp = W + 2, IMG = (long long)(H + 1) * Wp, G = (long long)N * IMG;
+  if (G + 2 * Wp + C3_MT >= 0x7FFFFFFFLL) return false;
+  const int NT = (CO & 127) == 0 ? 128 : 64;
+  const int pieces = (int)((C3_MT + 2 * Wp + 2 + 7) / 8);
+  const size_t lds = (size_t)pieces * 1024 + 2 * NT * 64 * 2;
+  if (lds > 80 * 1024) return false;                      // two workgroups per CU
+  C3Args p;
+  p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.y = (unsigned short*)y; p.stats = nullptr;
+  p.N = N; p.H = H; p.W = W; p.CI = CI; p.CO = CO;
+  p.Wp = (int)Wp; p.IMG = (int)IMG; p.G = (int)G;
+  p.tiles_m = (int)((G + C3_MT - 1) / C3_MT); p.tiles_n = CO / NT; p.pieces = pieces;
+  p.dIMG = make_fastdiv(p.IMG); p.dWp = make_fastdiv(p.Wp);
+  p.scale = p.shift = nullptr; p.residual = nullptr; p.relu = 0;
+  *out = p; *nt_out = NT; *lds_out = lds;
+  return true;
+}
+
 // Returns 1 when this kernel took the launch, 0 when the shape is outside its envelope (the caller then uses the
 // im2col GEMM), > 1 on a launch error.  x/y channel counts in the FORWARD sense of the call: dgrad = 1 swaps roles
 // (x = dy [N,H,W,Ko], y = dx [N,H,W,C], w [Ko,3,3,C]).
 extern "C" int dle_conv3x3_try(const void* x, const void* w, void* y, float* stats, long long stats_bytes, int N, int H,
                                int W, int C, int Ko, int dgrad, int dtype, hipStream_t stream) {
-  if (g_conv3x3_mode == 0) return 0;
-  const int CI = dgrad ? Ko : C, CO = dgrad ? C : Ko;
-  if ((CI & 63) || (CO & 63) || (dtype != DLE_F16 && dtype != DLE_BF16)) return 0;
-  // 7x7 images: a third of the 256-slot tile is padding and the layer is bound by the weight traffic per tile; the
-  // forward im2col GEMM measured 7 % faster there (tools/kbench/conv_bench), the data gradient 26 % slower
-  if (!dgrad && g_conv3x3_mode < 1 && H * W < 100) return 0;
-  if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y)) & 15) return 0;
-  const long long Wp = W + 2, IMG = (long long)(H + 1) * Wp, G = (long long)N * IMG;
-  if (G + 2 * Wp + C3_MT >= 0x7FFFFFFFLL) return 0;
-  const int NT = (CO & 127) == 0 ? 128 : 64;
-  const int pieces = (int)((C3_MT + 2 * Wp + 2 + 7) / 8);
-  const size_t lds = (size_t)pieces * 1024 + 2 * NT * 64 * 2;
-  if (lds > 80 * 1024) return 0;                          // two workgroups per CU
+  const int CO = dgrad ? C : Ko;
   C3Args p;
-  p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.y = (unsigned short*)y; p.stats = stats;
-  p.N = N; p.H = H; p.W = W; p.CI = CI; p.CO = CO;
-  p.Wp = (int)Wp; p.IMG = (int)IMG; p.G = (int)G;
-  p.tiles_m = (int)((G + C3_MT - 1) / C3_MT); p.tiles_n = CO / NT; p.pieces = pieces;
-  p.dIMG = make_fastdiv(p.IMG); p.dWp = make_fastdiv(p.Wp);
+  int NT;
+  size_t lds;
+  if (!c3_plan(x, w, y, N, H, W, dgrad ? Ko : C, CO, dgrad, dtype, &p, &NT, &lds)) return 0;
+  p.stats = stats;
   if (stats && stats_bytes < (long long)p.tiles_m * 2 * CO * 4) {
     dle_set_error("conv3x3: statistics buffer too small (%d tile rows)", p.tiles_m);
     return 2;
@@ -281,5 +359,33 @@ extern "C" int dle_conv3x3_try(const void* x, const void* w, void* y, float* sta
 #undef C3_PICK
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { dle_set_error("conv3x3 launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
+  return 1;
+}
+
+static long long g_c3_affine_launches = 0;
+// launches of the affine halo kernel by this process so far (tests assert that a call was NOT declined)
+extern "C" int64_t dle_conv3x3_affine_launch_count(void) { return __atomic_load_n(&g_c3_affine_launches, __ATOMIC_RELAXED); }
+
+// The forward halo kernel with the inference epilogue y = relu?(fmaf(scale, acc, shift) + residual); same envelope and return
+// convention as dle_conv3x3_try (+ 16-byte aligned scale / shift / residual).
+extern "C" int dle_conv3x3_affine_try(const void* x, const void* w, void* y, const float* scale, const float* shift,
+                                      const void* residual, int N, int H, int W, int C, int Ko, int dtype, int relu,
+                                      hipStream_t stream) {
+  if ((((uintptr_t)scale) | ((uintptr_t)shift) | ((uintptr_t)residual)) & 15) return 0;
+  if ((long long)N * H * W * Ko >= 0x7FFFFFFFLL) return 0;        // the epilogue keeps element offsets in 32 bits
+  C3Args p;
+  int NT;
+  size_t lds;
+  if (!c3_plan(x, w, y, N, H, W, C, Ko, 0, dtype, &p, &NT, &lds)) return 0;
+  p.scale = scale; p.shift = shift; p.residual = (const unsigned short*)residual; p.relu = relu;
+  dim3 grid((unsigned)(p.tiles_m * p.tiles_n)), block(256);
+#define C3_GO(DT, NTV) DLE_LAUNCH_LDS((conv3x3_kernel<DT, false, NTV, true>), grid, block, lds, stream, p)
+#define C3_PICK(DT) do { if (NT == 128) C3_GO(DT, 128); else C3_GO(DT, 64); } while (0)
+  if (dtype == DLE_F16) C3_PICK(DLE_F16); else C3_PICK(DLE_BF16);
+#undef C3_GO
+#undef C3_PICK
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { dle_set_error("conv3x3 affine launch failed: %s", hipGetErrorString(e)); return (int)e + 1000; }
+  __atomic_fetch_add(&g_c3_affine_launches, 1, __ATOMIC_RELAXED);
   return 1;
 }

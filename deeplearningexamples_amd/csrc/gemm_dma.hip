@@ -32,7 +32,7 @@ struct Gemm2Args {
   const unsigned short* A;
   const unsigned short* B;
   void* C;
-  void* aux;
+  void* aux;             // (PLAIN = 2, dle_conv2d_fwd_affine: the fp32 per-column scale; `bias` is the shift, `mask_src` the residual)
   const float* bias;
   const unsigned short* mask_src;
   int M, N, K;
@@ -171,6 +171,9 @@ __device__ __forceinline__ void epi_store8(const Gemm2Args& p, float* v, int m, 
 // loop (its LDS-DMA goes through inline asm), so hipcc's wait-count pass has nothing to drain: with the general epilogue in
 // the same code it inserts s_waitcnt vmcnt(0) at the head of every tile (a bias / addend load of some path might still be
 // in flight when a register is reused), which waits for the previous tile's STORES before the next DMA can be issued.
+// PLAIN = 2: the inference epilogue of dle_conv2d_fwd_affine on that same always-fast path (the launcher checks the alignment):
+// C = relu?(fmaf(scale[n], acc, bias[n]) + mask_src) with scale = (const float*)aux, act in {ACT_NONE, ACT_RELU, ACT_ADD, ACT_ADD_RELU}.  Its own instantiations:
+// the training kernels keep their registers and their bits.
 // BST = 1: the ReLU-mask / activation-derivative epilogues (ACT_RELU_BWD, ACT_MUL) also leave the column sums of their rounded
 // output (p.stats, p.stats_sums) -- the bias gradient of the layer whose activation derivative they apply.  A separate instantiation: the 8 extra live registers spill in the 256 x 256
 // kernel (8 -> 20 VGPRs), which the BERT / WaveGlow GEMMs must not pay for.
@@ -453,13 +456,25 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
 #pragma unroll
     for (int r = 0; r < 4; ++r) { fbias[r] = b0[r]; fbias[4 + r] = b1[r]; }
   }
+  float fscale[8];                       // PLAIN == 2 only
+#pragma unroll
+  for (int r = 0; r < 8; ++r) fscale[r] = 1.f;
+  if constexpr (PLAIN == 2) {
+    if (f_col_ok) {
+      const float4_t b0 = *(const float4_t*)(p.bias + n0 + f_nl), b1 = *(const float4_t*)(p.bias + n0 + f_nl + 4);
+      const float* scale = (const float*)p.aux;
+      const float4_t s0 = *(const float4_t*)(scale + n0 + f_nl), s1 = *(const float4_t*)(scale + n0 + f_nl + 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { fbias[r] = b0[r]; fbias[4 + r] = b1[r]; fscale[r] = s0[r]; fscale[4 + r] = s1[r]; }
+    }
+  }
   float st0[8], st1[8];                  // column sums / sums of squares over this thread's rows (p.stats only)
 #pragma unroll
   for (int r = 0; r < 8; ++r) { st0[r] = 0.f; st1[r] = 0.f; }
   auto fast_pass = [&](auto ACTC, int half) __attribute__((always_inline)) {
     constexpr int act = decltype(ACTC)::value;
     constexpr bool needs_src = act == ACT_RELU_BWD || act == ACT_ADD || act == ACT_GELU_BWD || act == ACT_TANH_BWD ||
-                               act == ACT_ADD_MASKED || act == ACT_MUL;
+                               act == ACT_ADD_MASKED || act == ACT_MUL || act == ACT_ADD_RELU;
     const float* e0 = epi + f_ml0 * TN;
     const int c4 = f_nl >> 2;
     const int olo = (c4 ^ f_ml0) << 2, ohi = ((c4 + 1) ^ f_ml0) << 2;
@@ -480,8 +495,13 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
       const int x = (it & 1) << 6;                       // row & 31 alternates between ml0 and ml0 + 16
       const float4_t lo = *(const float4_t*)(e + (olo ^ x)), hi = *(const float4_t*)(e + (ohi ^ x));
       float v[8];
+      if constexpr (PLAIN == 2) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { v[r] = lo[r] + fbias[r]; v[4 + r] = hi[r] + fbias[4 + r]; }
+        for (int r = 0; r < 4; ++r) { v[r] = __builtin_fmaf(fscale[r], lo[r], fbias[r]); v[4 + r] = __builtin_fmaf(fscale[4 + r], hi[r], fbias[4 + r]); }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { v[r] = lo[r] + fbias[r]; v[4 + r] = hi[r] + fbias[4 + r]; }
+      }
       if constexpr (act == ACT_GELU_DAUX) {
         float dv[8];
 #pragma unroll
@@ -509,6 +529,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
           const float y = yv[r];
           if constexpr (act == ACT_RELU_BWD) v[r] = y > 0.f ? v[r] : 0.f;
           else if constexpr (act == ACT_ADD) v[r] += y;
+          else if constexpr (act == ACT_ADD_RELU) { v[r] += y; v[r] = v[r] > 0.f ? v[r] : 0.f; }
           else if constexpr (act == ACT_MUL) v[r] *= y;
           else if constexpr (act == ACT_ADD_MASKED) { if ((mbits >> r) & 1u) v[r] += y; }
           else if constexpr (act == ACT_TANH_BWD) v[r] *= (1.f - y * y);
@@ -673,6 +694,15 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : (NSTAGE == 1 ? 4 : 2)) v
         *(float4_t*)(c + it * step) = lo;
         *(float4_t*)(c + it * step + 4) = hi;
       }
+    }
+    continue;
+  }
+  if constexpr (PLAIN == 2) {
+    switch (p.act) {
+      case ACT_NONE: fast_pass(std::integral_constant<int, ACT_NONE>(), half); break;
+      case ACT_RELU: fast_pass(std::integral_constant<int, ACT_RELU>(), half); break;
+      case ACT_ADD: fast_pass(std::integral_constant<int, ACT_ADD>(), half); break;
+      default: fast_pass(std::integral_constant<int, ACT_ADD_RELU>(), half); break;
     }
     continue;
   }
@@ -1084,6 +1114,52 @@ extern "C" int dle_conv2d_fwd(const void* x, const void* w, void* y, const float
   p.out_dtype = out_dtype; p.act = act; p.splitk = 1; p.accumulate = 0; p.alpha = 1.f;
   p.cg = make_geom(H, W, C, P, Q, R, S, stride, pad, Ko);
   return launch_gemm(p, dtype, 2, 0, 0, stream);
+}
+
+// ---- inference: the convolution with the evaluation-mode BatchNorm (+ residual, + ReLU) in its epilogue ----------------------
+// Replaces cuDNN conv fwd + the eval-mode nn.BatchNorm2d (+ `out += residual`) + nn.ReLU behind it
+// (Classification/ConvNets/image_classification/models/resnet.py:148-175 under model.eval(), classify.py:79-99).
+//   y[n,p,q,ko] = round16( relu?( fmaf(scale[ko], acc, shift[ko]) + float(residual[n,p,q,ko]) ) )
+// acc: the fp32 accumulator over the unmodified 16-bit weights.  Routes: 3x3 / stride 1 / pad 1 on the halo-tile kernel
+// (conv3x3.hip, AFF) inside its envelope; 1x1 / stride 1 as a plain [N*H*W, C] x [Ko, C] matrix product and every other
+// geometry as implicit GEMM on the 128x128 tile kernel's PLAIN = 2 epilogue.  (The persistent 256x256 kernel and the streaming
+// kernel of gemm_expand.hip are not routed to: tools/rn50_infer_perf.py times whole networks -- 0.51-0.72 of the two-launch path's
+// time at batch 1..256, DESIGN.md section 4h -- and no per-unit measurement says they should be.)
+// No allocation, no synchronisation.
+extern "C" int dle_conv2d_fwd_affine(const void* x, const void* w, void* y, const float* scale, const float* shift,
+                                     const void* residual, int N, int H, int W, int C, int Ko, int R, int S, int stride,
+                                     int pad, int dtype, int relu, hipStream_t stream) {
+  DLE_CHECK_ARG(R > 0 && S > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S, "conv2d_fwd_affine: bad geometry");
+  const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+  if (int rc = conv_check("conv2d_fwd_affine", N, H, W, C, Ko, R, S, stride, pad, P, Q, dtype)) return rc;
+  DLE_CHECK_ARG(x && w && y && scale && shift, "conv2d_fwd_affine: null pointer");
+  DLE_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)scale) | ((uintptr_t)shift) | ((uintptr_t)residual)) & 15) == 0,
+                "conv2d_fwd_affine: every operand must be 16-byte aligned");
+  const long long M = (long long)N * P * Q;
+  DLE_CHECK_ARG(M < 0x7FFFFFFFLL && (long long)R * S * C < 0x7FFFFFFFLL, "conv2d_fwd_affine: too many output pixels");
+  if (R == 3 && S == 3 && stride == 1 && pad == 1)
+    DLE_TRY(dle_conv3x3_affine_try(x, w, y, scale, shift, residual, N, H, W, C, Ko, dtype, relu, stream), return 0);
+  const bool matrix = R == 1 && S == 1 && stride == 1 && pad == 0 && (long long)C * BM * 2 <= 0x7FFFFFFFLL;
+  Gemm2Args p = {};
+  p.A = (const unsigned short*)x; p.B = (const unsigned short*)w; p.C = y; p.bias = shift; p.aux = (void*)scale;
+  p.mask_src = (const unsigned short*)residual;
+  p.M = (int)M; p.N = Ko; p.K = R * S * C; p.lda = matrix ? C : 0; p.ldb = (long long)R * S * C; p.ldc = Ko;
+  p.out_dtype = dtype; p.splitk = 1; p.accumulate = 0; p.alpha = 1.f;
+  p.act = residual ? (relu ? ACT_ADD_RELU : ACT_ADD) : (relu ? ACT_RELU : ACT_NONE);
+  p.cg = make_geom(H, W, C, P, Q, R, S, stride, pad, Ko);
+  p.gm = dle_gemm_gm();
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+  const int resident = 2 * 256;                     // the persistent walk of launch_gemm (plain matrix operands only)
+  p.persist = matrix && tiles > resident;
+  dim3 grid(p.persist ? resident : tiles, 1, 1), block(256);
+  const size_t lds = GEMM2_LDS_BYTES;
+#define GOA(DT) do { if (matrix) hipLaunchKernelGGL((gemm2_kernel<DT, 0, 0, 2, 0, 2>), grid, block, lds, stream, p); \
+                     else hipLaunchKernelGGL((gemm2_kernel<DT, 2, 0, 2, 0, 2>), grid, block, lds, stream, p); } while (0)
+  if (dtype == DLE_F16) GOA(DLE_F16); else GOA(DLE_BF16);
+#undef GOA
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { dle_set_error("conv2d_fwd_affine launch failed: %s", hipGetErrorString(e)); return (int)e; }
+  return 0;
 }
 
 // row limit of the ping-pong kernel in dle_conv2d_fwd_colstats: the 14 x 14 and 7 x 7 stages at batch 256

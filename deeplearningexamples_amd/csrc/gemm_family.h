@@ -20,11 +20,14 @@ enum { ACT_NONE = DLE_ACT_NONE, ACT_RELU = DLE_ACT_RELU, ACT_GELU = DLE_ACT_GELU
        // the ReLU of a linear layer as ONE BIT per element (ping-pong kernel only: dle_gemm8_relu_bits_try / ..._bwd_bits_try):
        // forward (EPI 1): bias + ReLU, aux RECEIVES the keep bits (bit (m N + n) & 7 of byte (m N + n) >> 3 = rounded output > 0);
        // backward (EPI 2): C = product where the bit is set, aux = those bits, NO source tensor is read
-       ACT_RELU_BITS = 11, ACT_RELU_BWD_BITS = 12 };
+       ACT_RELU_BITS = 11, ACT_RELU_BWD_BITS = 12,
+       // inference (dle_conv2d_fwd_affine; the PLAIN = 2 tile kernels of gemm_dma.hip only): C = relu(scale * acc + shift + mask_src)
+       ACT_ADD_RELU = 13 };
 
 // epilogues that read the source tensor `mask_src` (same shape / pitch / dtype as C)
 inline bool act_needs_src(int act) {
-  return act == ACT_RELU_BWD || act == ACT_ADD || act == ACT_GELU_BWD || act == ACT_TANH_BWD || act == ACT_ADD_MASKED || act == ACT_MUL;
+  return act == ACT_RELU_BWD || act == ACT_ADD || act == ACT_GELU_BWD || act == ACT_TANH_BWD || act == ACT_ADD_MASKED || act == ACT_MUL ||
+         act == ACT_ADD_RELU;
 }
 
 // the streaming kernel of gemm_expand.hip numbers its three epilogues itself (template parameter ACT of gemm_expand_kernel)
@@ -83,6 +86,9 @@ int dle_gemm_expand_groups(int M, int N, int K);
 int dle_conv3x3_try(const void* x, const void* w, void* y, float* stats, long long stats_bytes, int N, int H, int W, int C, int Ko,
                     int dgrad, int dtype, hipStream_t stream);
 int dle_conv3x3_tiles(int N, int H, int W);
+// ... its inference instantiations: y = relu?(fmaf(scale[ko], acc, shift[ko]) + residual), forward only
+int dle_conv3x3_affine_try(const void* x, const void* w, void* y, const float* scale, const float* shift, const void* residual, int N,
+                           int H, int W, int C, int Ko, int dtype, int relu, hipStream_t stream);
 int dle_conv3x3_wgrad_try(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int dtype, int accumulate,
                           void* workspace, int64_t workspace_bytes, hipStream_t stream);
 }

@@ -639,6 +639,32 @@ def conv2d_fwd(x, w, stride=1, pad=0, bias=None, act=C.ACT_NONE, out=None, out_d
     return out
 
 
+def conv2d_fwd_affine(x, w, scale, shift, stride=1, pad=0, residual=None, relu=True, out=None):
+    """Inference unit in one launch: y = relu?(scale[ko] * conv(x, w) + shift[ko] (+ residual)) on the fp32 accumulator, rounded
+    once.  x [N,H,W,C], w [Ko,R,S,C] (16-bit, contiguous), scale / shift fp32 [Ko], residual [N,P,Q,Ko] or None -> y [N,P,Q,Ko]."""
+    C.require_cuda(x, w, scale, shift, residual, out)
+    n, h, wd, c = x.shape
+    ko, r, s, c2 = w.shape
+    p, q = _conv_out(h, wd, r, s, stride, pad)
+    if c2 != c or not x.is_contiguous() or not w.is_contiguous() or x.dtype != w.dtype:
+        raise ValueError("conv2d_fwd_affine: x must be NHWC-contiguous and w KRSC-contiguous with matching C/dtype")
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.numel() != ko or not t.is_contiguous():
+            raise ValueError("conv2d_fwd_affine: scale / shift must be contiguous fp32 [Ko]")
+    if residual is not None and (tuple(residual.shape) != (n, p, q, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
+        raise ValueError("conv2d_fwd_affine: residual must be a contiguous [N,P,Q,Ko] tensor of x's dtype")
+    if out is None:
+        out = torch.empty((n, p, q, ko), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (n, p, q, ko) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("conv2d_fwd_affine: out must be a contiguous [N,P,Q,Ko] tensor of x's dtype")
+    C.annotate(flops=2.0 * n * p * q * ko * r * s * c, tag="affine %dx%dx%dx%d k%d %dx%d s%d%s" % (n, h, wd, c, ko, r, s, stride,
+                                                                                                "+res" if residual is not None else ""),
+               bytes=float(x.numel() + w.numel() + out.numel() * (2 if residual is not None else 1)) * 2)
+    C.call("dle_conv2d_fwd_affine", C.ptr(x), C.ptr(w), C.ptr(out), C.ptr(scale), C.ptr(shift), C.ptr(residual), n, h, wd, c, ko,
+           r, s, stride, pad, C.dt(x), int(bool(relu)), C.stream())
+    return out
+
+
 def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, addend=None, out=None):
     """dy [N,P,Q,Ko], w [Ko,R,S,C] -> dx [N,H,W,C] (+ addend)."""
     C.require_cuda(dy, w, addend, out)

@@ -192,6 +192,20 @@ int dle_conv2d_fwd(const void* x, const void* w, void* y, const float* bias, int
                    hipStream_t stream);
 int dle_conv2d_dgrad(const void* dy, const void* w, void* dx, const void* addend, int N, int H, int W, int C,
                      int Ko, int R, int S, int stride, int pad, int dtype, hipStream_t stream);
+/* Inference: the convolution with the evaluation-mode BatchNorm, the residual add and the ReLU in its epilogue -- one launch
+ * instead of conv + BatchNorm-apply, the activation is written once and rounded once.  Replaces, under model.eval(),
+ *   Classification/ConvNets/image_classification/models/resnet.py:148-175 (conv -> bn -> relu, `out += residual`),
+ *   classify.py:79-99 / main.py --evaluate (the forward those run)
+ *   y[n,p,q,ko] = round16( relu?( fmaf(scale[ko], acc, shift[ko]) + float(residual[n,p,q,ko]) ) )
+ * acc: the fp32 accumulator over the UNMODIFIED 16-bit KRSC weights (no folded copy); scale / shift fp32 [Ko]
+ * (scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale); residual 16-bit [N,P,Q,Ko] or NULL;
+ * round-to-nearest-even, once.  Every operand 16-byte aligned, C and Ko multiples of 8.  No allocation, no synchronisation
+ * (graph capturable).  3x3 / stride 1 / pad 1 with C, Ko multiples of 64 runs on the halo-tile kernel (csrc/conv3x3.hip);
+ * dle_conv3x3_affine_launch_count(): launches of that kernel by this process so far (tests assert it was NOT declined).      */
+int dle_conv2d_fwd_affine(const void* x, const void* w, void* y, const float* scale, const float* shift,
+                          const void* residual, int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad,
+                          int dtype, int relu, hipStream_t stream);
+int64_t dle_conv3x3_affine_launch_count(void);
 int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int R, int S,
                      int stride, int pad, int dtype, int splitk, int accumulate, void* workspace,
                      int64_t workspace_bytes, hipStream_t stream);

@@ -1,0 +1,155 @@
+"""Host side of the ResNet-50 inference path (convnets/infer.py, classify.py, checkpoint2model.py): checkpoint forms, command
+lines, the BatchNorm fold and the printed lines.  CPU only."""
+import ast
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import _ref_import as R  # noqa: E402
+
+from deeplearningexamples_amd.convnets import checkpoint2model, classify  # noqa: E402
+from deeplearningexamples_amd.convnets.infer import ResNet50Classifier, fold_bn, state_from_checkpoint  # noqa: E402
+
+needs_ref = pytest.mark.skipif(not R.have_reference(), reason="reference tree not mounted")
+
+
+def _synthetic_checkpoint(prefix=""):
+    g = torch.Generator().manual_seed(5)
+    sd = {prefix + "conv1.weight": torch.randn(4, 3, 7, 7, generator=g), prefix + "bn1.running_var": torch.rand(4, generator=g),
+          prefix + "fc.bias": torch.randn(10, generator=g)}
+    ema = {k: v + 1.0 for k, v in sd.items()}
+    return {"epoch": 3, "best_prec1": 12.5, "state_dict": sd, "state_dict_ema": ema, "optimizer": {"state": {}}}
+
+
+@pytest.mark.parametrize("ema", [False, True], ids=["model", "ema"])
+def test_checkpoint2model_writes_the_bare_state_dict(tmp_path, ema, capsys):
+    ck = _synthetic_checkpoint(prefix="module.")
+    src, dst = str(tmp_path / "checkpoint_0003.pth.tar"), str(tmp_path / "weights.pth")
+    torch.save(ck, src)
+    checkpoint2model.main(["--checkpoint-path", src, "--weight-path", dst] + (["--ema"] if ema else []))
+    assert "12.5" in capsys.readouterr().out
+    out = torch.load(dst, map_location="cpu")
+    want = ck["state_dict_ema" if ema else "state_dict"]
+    assert sorted(out) == sorted(k[len("module."):] for k in want)
+    for k, v in want.items():
+        assert torch.equal(out[k[len("module."):]], v)
+    # the file it wrote is itself an accepted form (a bare state dict), and so is a `module.`-prefixed one
+    assert sorted(state_from_checkpoint(out)) == sorted(out)
+    assert sorted(state_from_checkpoint(ck["state_dict"])) == sorted(out)
+
+
+def test_checkpoint2model_ema_without_an_averaged_model_fails(tmp_path):
+    ck = _synthetic_checkpoint()
+    del ck["state_dict_ema"]
+    src = str(tmp_path / "c.pth.tar")
+    torch.save(ck, src)
+    with pytest.raises(SystemExit) as e:
+        checkpoint2model.main(["--checkpoint-path", src, "--weight-path", str(tmp_path / "w.pth"), "--ema"])
+    assert "state_dict_ema" in str(e.value) and not os.path.exists(str(tmp_path / "w.pth"))
+    with pytest.raises(ValueError):
+        state_from_checkpoint([1, 2, 3])
+
+
+def _flags_of(path, function="add_parser_arguments"):
+    """Every option string of the parser.add_argument calls in `function` of the file, read with ast (nothing is imported)."""
+    tree = ast.parse(open(path).read())
+    fn = next(n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == function)
+    flags = set()
+    for call in ast.walk(fn):
+        if isinstance(call, ast.Call) and isinstance(call.func, ast.Attribute) and call.func.attr == "add_argument":
+            flags |= {a.value for a in call.args if isinstance(a, ast.Constant) and isinstance(a.value, str) and a.value.startswith("-")}
+    return flags
+
+
+def _parser(mod):
+    import argparse
+    return mod.add_parser_arguments(argparse.ArgumentParser())
+
+
+@needs_ref
+def test_parsers_accept_every_flag_of_the_reference_scripts():
+    root = os.path.join(R.REF, "PyTorch", "Classification", "ConvNets")
+    for mod, name in ((classify, "classify.py"), (checkpoint2model, "checkpoint2model.py")):
+        ref_flags = _flags_of(os.path.join(root, name))
+        assert len(ref_flags) >= 3
+        ours = {s for a in _parser(mod)._actions for s in a.option_strings}
+        assert ref_flags <= ours, "%s: flags of the reference missing here: %s" % (name, sorted(ref_flags - ours))
+    # ... and the model flag classify.py takes through the model's own parser
+    assert "--pretrained-from-file" in {s for a in _parser(classify)._actions for s in a.option_strings}
+
+
+def test_classify_flags_and_rejections():
+    p = _parser(classify)
+    a = p.parse_args(["--image", "x.npy"])
+    assert (a.arch, a.image_size, a.precision, a.cpu, a.amp_dtype, a.synset_mapping) == ("resnet50", 224, "AMP", False, "fp16", None)
+    classify.reject_unbuilt(a)
+    for argv, word in ((["--image", "x", "--arch", "efficientnet-b0"], "resnet50"), (["--image", "x", "-a", "resnext101-32x4d"], "resnet50"),
+                       (["--image", "x", "--cpu"], "--cpu"), (["--image", "x", "--precision", "FP32"], "16 bits"), ([], "--image")):
+        with pytest.raises(SystemExit) as e:
+            classify.reject_unbuilt(p.parse_args(argv))
+        msg = str(e.value)
+        assert word in msg and "\n" not in msg, msg
+    with pytest.raises(SystemExit):
+        p.parse_args(["--image", "x", "--arch", "vgg16"])           # not an architecture of the reference either: argparse's error
+
+
+def test_classifier_rejects_fp32_like_main():
+    with pytest.raises(ValueError) as e:
+        ResNet50Classifier({}, dtype=torch.float32)
+    assert "16 bits" in str(e.value) and "fp32 / TF32" in str(e.value)
+    with pytest.raises(ValueError):
+        ResNet50Classifier({}, dtype=torch.float64)
+
+
+def test_fold_bn_closed_form_against_float64():
+    g = torch.Generator().manual_seed(11)
+    c = 512
+    gamma, beta, mean = torch.randn(c, generator=g), torch.randn(c, generator=g), torch.randn(c, generator=g) * 3
+    var = torch.rand(c, generator=g) * 4 + 1e-3
+    var[:4] = torch.tensor([1e-12, 1e-9, 0.0, 3e-7])                # tiny running_var: scale ~ gamma / sqrt(eps) = 316 gamma
+    gamma[:4] = torch.tensor([300.0, -250.0, 400.0, 1.0])
+    eps = 1e-5
+    scale, shift = fold_bn(gamma, beta, mean, var, eps)
+    assert scale.dtype == shift.dtype == torch.float32 and scale.is_contiguous() and shift.is_contiguous()
+    s64 = gamma.double() / torch.sqrt(var.double() + eps)
+    h64 = beta.double() - mean.double() * s64
+    # rsqrt, one multiply; one multiply, one subtract: a few fp32 roundings, relative to the terms' magnitudes
+    assert float(((scale.double() - s64).abs() / s64.abs()).max()) <= 4 * 2.0 ** -24
+    assert bool(((shift.double() - h64).abs() <= 6 * 2.0 ** -24 * (beta.double().abs() + (mean.double() * s64).abs())).all())
+    # a weight FOLDED into fp16 (w * scale) would overflow here; the fp32 coefficient does not
+    assert float(scale[0]) > 65504 and bool(torch.isfinite(scale).all())
+    assert bool(torch.isinf((torch.ones(1) * scale[0]).half()).all())
+    # the same map as evaluation-mode BatchNorm
+    x = torch.randn(8, c, generator=g).double()
+    bn = (x - mean.double()) / torch.sqrt(var.double() + eps) * gamma.double() + beta.double()
+    got = x * scale.double() + shift.double()
+    assert bool(((got - bn).abs() <= 1e-5 * (bn.abs() + (mean.double() * s64).abs() + 1)).all())
+
+
+def test_top5_lines():
+    probs = torch.tensor([0.05, 0.5, 0.0, 0.25, 0.125, 0.0749, 0.0001])
+    idx = torch.topk(probs, 5).indices
+    lines = classify.format_top5("img.npy", probs, idx)
+    assert lines == ["img.npy", "class 1: 50.0%", "class 3: 25.0%", "class 4: 12.5%", "class 5: 7.5%", "class 0: 5.0%"]
+    names = ["n%d, name %d" % (i, i) for i in range(7)]
+    assert classify.format_top5("p", probs, idx, names)[1] == "n1, name 1: 50.0%"
+
+
+def test_read_image_array_form_and_preprocess(tmp_path):
+    import numpy as np
+    a = (np.arange(300 * 400 * 3) % 251).astype(np.uint8).reshape(300, 400, 3)
+    p = str(tmp_path / "img.npy")
+    np.save(p, a)
+    assert np.array_equal(classify.read_image(p), a)
+    np.save(str(tmp_path / "gray.npy"), a[..., 0])
+    assert classify.read_image(str(tmp_path / "gray.npy")).shape == (300, 400, 3)
+    np.save(str(tmp_path / "bad.npy"), a.astype(np.float32))
+    with pytest.raises(SystemExit):
+        classify.read_image(str(tmp_path / "bad.npy"))
+    x = classify.preprocess(a, 64, torch.device("cpu"))
+    assert tuple(x.shape) == (1, 3, 64, 64) and x.dtype == torch.float32 and x.is_contiguous()
+    lo, hi = (0 - 0.485) / 0.229, (1 - 0.406) / 0.225
+    assert float(x.min()) >= lo - 1e-3 and float(x.max()) <= hi + 1e-3
