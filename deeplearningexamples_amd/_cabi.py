@@ -142,6 +142,7 @@ _SIGS = {
     "dle_layernorm_workspace_bytes": (c_i64, [c_int]),
     "dle_layernorm_bwd": (c_int, [c_void_p] * 8 + [c_i64, c_int, c_int, c_void_p, c_i64, c_int, c_void_p]),
     "dle_embed_sum": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_void_p]),
+    "dle_embed_sum_packed": (c_int, [c_void_p] * 7 + [c_i64, c_int, c_int, c_void_p]),
     "dle_embed_scatter_add": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
     "dle_rows_select_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_int,
                                     c_void_p]),
@@ -162,6 +163,9 @@ _SIGS = {
     "dle_attention_fwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float, c_float, c_u64, c_u64, c_void_p, c_int, c_void_p]),
     "dle_attention_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_float, c_u64, c_u64, c_void_p, c_int, c_void_p]),
     "dle_attention_bwd_keep": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_float, c_u64, c_u64, c_void_p, c_int, c_void_p]),
+    "dle_attention_varlen_supported": (c_int, [c_int, c_int]),
+    "dle_attention_fwd_varlen": (c_int, [c_void_p] * 3 + [c_int, c_int, c_i64, c_int, c_int, c_float, c_int, c_void_p]),
+    "dle_attention_varlen_launch_count": (c_u64, []),
     "dle_colsum": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "dle_colsum_batched_workspace_bytes": (c_i64, [c_int, c_i64, c_int]),
     "dle_colsum_batched": (c_int, [c_void_p, c_int, c_i64, c_int, c_i64, c_int, c_void_p, c_i64, c_void_p]),

@@ -950,3 +950,194 @@ extern "C" int dle_attention_bwd_keep(const void* qkv, const void* dctx, const f
   return attention_bwd_impl(qkv, dctx, mask_add, stats, keep_mask, dqkv, colsum_partial, B, S, heads, head_dim, scale, p, seed, offset,
                             offset_base, dtype, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Packed (variable-length) forward attention for inference: qkv [T, 3H] holds the sequences back to back, sequence b owns rows
+// cu_seqlens[b] .. cu_seqlens[b + 1] - 1, and the length is the mask -- no mask_add, no dropout, no statistics output
+// (BertSelfAttention.forward under model.eval(), modeling.py:340-384, on the sum(len) real rows of a batch that
+// extract_features.py:262-294 pads to [B, max_seq_length]).  The walk is attn_fwd_long_kernel's: one workgroup per (sequence,
+// head, 128-query block), keys through LDS in ascending 128-key blocks, pass 1 = online max / sum, pass 2 = the final
+// statistics, the same per-lane loop order -- so a sequence's rows carry the bits the padded kernels give it under a
+// 0 / -10000 mask.  What differs:
+//   * the grid is B * heads * ceil(max_seqlen / 128); a workgroup whose query block starts at or past its sequence's length
+//     returns before any barrier, LDS write or tile load (the test is on blockIdx and two scalar loads: workgroup-uniform);
+//   * only ceil(len / 128) key blocks are walked; in the last one the keys at or past len (the next sequence's rows, or rows
+//     past the buffer) are set to -inf before the max, so __expf gives exactly 0 for them whatever they hold;
+//   * the buffer resource ends with the sequence's last row and never past the real byte size of qkv: the next sequence's
+//     rows and rows past total_tokens read as zero (no fault, and 0 * V of a masked key is 0 even where that row holds NaN);
+//   * rows at or past len of the staged 32-row slab belong to the next sequence: the store is guarded per row;
+//   * len is clamped to [0, max_seqlen], the first row to [0, total_tokens] and every stored row to total_tokens: a wrong
+//     cu_seqlens table gives wrong answers but touches nothing outside qkv / ctx.
+struct AttnVarlenArgs {
+  const unsigned short* qkv;    // [T, 3H]
+  const int* cu;                // [B + 1] row offsets, cu[0] = 0
+  unsigned short* ctx;          // [T, H]
+  int nh, H, max_seqlen, nqb;   // nqb = ceil(max_seqlen / 128) query blocks per (sequence, head)
+  long long total;              // T
+  unsigned qkv_bytes;           // T * 3H * 2 (< 2^32: checked by the entry point)
+  float scale;
+};
+
+// scaled scores of one key block with `rem` keys of the sequence left in it (>= 128 in every block but the last): keys at or
+// past rem -> -inf.  One code path for full and partial blocks; the select between the product and the subtraction of the
+// row max also keeps the two from being contracted, so a valid score is the rounded product the padded kernels compute.
+__device__ __forceinline__ void at_block_scores_masked(float16_t* s, float scale, int hf, int rem) {
+  const int remh = rem - 4 * hf;
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float x = s[kb][r] * scale;
+      s[kb][r] = (kb * 32 + (r & 3) + 8 * (r >> 2)) < remh ? x : -INFINITY;
+    }
+}
+
+// at_store_rows for the first `nrows` rows of the slab only
+__device__ __forceinline__ void at_store_rows_guarded(const unsigned short* stg, unsigned short* out, long long ld, int lane, int nrows) {
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row = it * 8 + (lane >> 3), c = lane & 7;
+    const ushort8_t v = *(const ushort8_t*)(stg + row * AT_D + ((c ^ (row & 7)) << 3));
+    if (row < nrows) *(ushort8_t*)(out + row * ld + c * 8) = v;
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void attn_fwd_varlen_kernel(AttnVarlenArgs p) {
+  const int qb = blockIdx.x % p.nqb, bh = blockIdx.x / p.nqb, b = bh / p.nh, h = bh - b * p.nh;
+  long long start = p.cu[b];
+  long long len_ll = (long long)p.cu[b + 1] - start;
+  start = start < 0 ? 0 : (start > p.total ? p.total : start);
+  const int len = (int)(len_ll < 0 ? 0 : (len_ll > p.max_seqlen ? p.max_seqlen : len_ll));
+  if (qb * AT_S >= len) return;                              // workgroup-uniform: before any barrier, LDS write or tile load
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned short* Qt = (unsigned short*)smem_raw;
+  unsigned short* Kt = Qt + AT_TILE;
+  unsigned short* Vt = Kt + AT_TILE;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5;
+  const int nkb = (len + AT_S - 1) / AT_S;
+  const unsigned ld = (unsigned)p.H * 3u * 2u;
+  const unsigned seq_base = (unsigned)((start * 3 * p.H + h * AT_D) * 2);                        // row 0 of the sequence, q columns
+  // the resource ends with the sequence's last row (never past qkv): the rows of the next sequence that a 128-row tile covers
+  // read as zero, so the 0 * V terms of the masked keys are 0 whatever those rows hold, Inf and NaN included
+  const long long end_ll = start + len < p.total ? start + len : p.total;
+  const unsigned long long seq_end = (unsigned long long)end_ll * ld;
+  const unsigned rs_bytes = seq_end < p.qkv_bytes ? (unsigned)seq_end : p.qkv_bytes;
+  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkv, 0, rs_bytes, 0x00020000);
+  at_load_tile(rs, seq_base + (unsigned)(qb * AT_S) * ld, ld, Qt, wave, lane);
+  auto scores = [&](float16_t* s) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const ushort8_t bq = at_frag_rows(Qt, wave * 32, ks, lane);
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) s[kb] = Mfma32x16<DT>::run(at_frag_rows(Kt, kb * 32, ks, lane), bq, s[kb]);
+    }
+  };
+  // ---- pass 1: online row max / sum over the sequence's key blocks
+  float m_run = -INFINITY, l_run = 0.f;
+  for (int j = 0; j < nkb; ++j) {
+    if (j > 0) __syncthreads();                             // every wave is done with the previous K block
+    at_load_tile(rs, seq_base + (unsigned)p.H * 2u + (unsigned)(j * AT_S) * ld, ld, Kt, wave, lane);
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+    float16_t s[4];
+    scores(s);
+    at_block_scores_masked(s, p.scale, hf, len - j * AT_S);
+    float v = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) v = fmaxf(v, s[kb][r]);
+    v = fmaxf(v, __shfl_xor(v, 32, 64));
+    const float m_new = fmaxf(m_run, v);
+    float sum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sum += __expf(s[kb][r] - m_new);
+    sum += __shfl_xor(sum, 32, 64);
+    l_run = l_run * __expf(m_run - m_new) + sum;
+    m_run = m_new;
+  }
+  const float mx = m_run, inv = 1.0f / l_run;
+  // ---- pass 2: probabilities with the final statistics, context
+  float16_t o[2];
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+  for (int j = 0; j < nkb; ++j) {
+    __syncthreads();
+    at_load_tile(rs, seq_base + (unsigned)p.H * 2u + (unsigned)(j * AT_S) * ld, ld, Kt, wave, lane);
+    at_load_tile(rs, seq_base + (unsigned)p.H * 4u + (unsigned)(j * AT_S) * ld, ld, Vt, wave, lane);
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+    float16_t s[4];
+    scores(s);
+    at_block_scores_masked(s, p.scale, hf, len - j * AT_S);
+    ushort8_t pd[8];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      float v[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) v[r] = __expf(s[kb][r] - mx) * inv;
+      pd[kb * 2] = pack8<DT>(v);
+      pd[kb * 2 + 1] = pack8<DT>(v + 8);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj)
+#pragma unroll
+      for (int db = 0; db < 2; ++db) o[db] = Mfma32x16<DT>::run(at_frag_cols<true>(Vt, db * 32, jj, lane), pd[jj], o[db]);
+  }
+  __syncthreads();                                          // (a faster wave must not stage over K / V rows others still read: Q only)
+  unsigned short* stg = Qt + wave * 32 * AT_D;
+  at_stage_block<DT>(stg, o[0], 0, lane);
+  at_stage_block<DT>(stg, o[1], 1, lane);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  // the slab's rows inside the sequence AND inside ctx: the rest belong to the next sequence or lie past the tensor
+  const long long row0 = start + qb * AT_S + wave * 32;
+  const long long in_seq = (long long)len - (qb * AT_S + wave * 32), in_buf = p.total - row0;
+  const long long nrows_ll = in_seq < in_buf ? in_seq : in_buf;
+  const int nrows = (int)(nrows_ll < 0 ? 0 : (nrows_ll > 32 ? 32 : nrows_ll));
+  at_store_rows_guarded(stg, p.ctx + row0 * p.H + h * AT_D, p.H, lane, nrows);
+}
+
+static unsigned long long g_attn_varlen_launches = 0;
+
+extern "C" int dle_attention_varlen_supported(int max_seqlen, int head_dim) {
+  return (head_dim == AT_D && max_seqlen >= 1 && max_seqlen <= 1024) ? 1 : 0;
+}
+extern "C" uint64_t dle_attention_varlen_launch_count(void) { return __atomic_load_n(&g_attn_varlen_launches, __ATOMIC_RELAXED); }
+
+// ctx[T, H] = softmax(q k^T * scale) v per (sequence, head) over each sequence's own rows of the packed qkv [T, 3H].
+// Offsets into qkv are 32-bit and a tile reaches up to 127 rows past a sequence's last: (total_tokens + 127) * 3H * 2 >= 2^32
+// is an error.
+extern "C" int dle_attention_fwd_varlen(const void* qkv, const int32_t* cu_seqlens, void* ctx, int B, int max_seqlen,
+                                        int64_t total_tokens, int heads, int head_dim, float scale, int dtype, hipStream_t stream) {
+  DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "attention_fwd_varlen: 16-bit activations only");
+  DLE_CHECK_ARG(dle_attention_varlen_supported(max_seqlen, head_dim),
+                "attention_fwd_varlen: built for 64-wide heads and 1 <= max_seqlen <= 1024 (got %d, %d)", head_dim, max_seqlen);
+  DLE_CHECK_ARG(B > 0 && heads > 0 && total_tokens > 0, "attention_fwd_varlen: bad batch / heads / total_tokens");
+  DLE_CHECK_ARG(heads <= 4096 && total_tokens < (1LL << 32) &&
+                    (unsigned long long)(total_tokens + AT_S - 1) * 3ULL * (unsigned)(heads * head_dim) * 2ULL < (1ULL << 32),
+                "attention_fwd_varlen: QKV activation of 4 GiB or more (32-bit offsets)");
+  const int nqb = (max_seqlen + AT_S - 1) / AT_S;
+  DLE_CHECK_ARG((long long)B * heads * nqb < 0x7FFFFFFFLL, "attention_fwd_varlen: grid too large");
+  DLE_CHECK_ARG(qkv && cu_seqlens && ctx, "attention_fwd_varlen: null pointer");
+  DLE_CHECK_ARG(((((uintptr_t)qkv) | ((uintptr_t)ctx)) & 15) == 0, "attention_fwd_varlen: tensors must be 16-byte aligned");
+  AttnVarlenArgs a = {};
+  a.qkv = (const unsigned short*)qkv; a.cu = cu_seqlens; a.ctx = (unsigned short*)ctx; a.nh = heads; a.H = heads * head_dim;
+  a.max_seqlen = max_seqlen; a.nqb = nqb; a.total = total_tokens;
+  a.qkv_bytes = (unsigned)((unsigned long long)total_tokens * 3ULL * (unsigned)a.H * 2ULL); a.scale = scale;
+  const size_t lds = 3 * AT_TILE * 2;
+  const dim3 grid(B * heads * nqb);
+  if (dtype == DLE_F16) hipLaunchKernelGGL(attn_fwd_varlen_kernel<DLE_F16>, grid, dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL(attn_fwd_varlen_kernel<DLE_BF16>, grid, dim3(256), lds, stream, a);
+  DLE_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_attn_varlen_launches, 1, __ATOMIC_RELAXED);
+  return 0;
+}

@@ -490,6 +490,46 @@ extern "C" int dle_embed_sum(const float* word, const float* pos, const float* t
   return 0;
 }
 
+// z[t] = word[ids[t]] + pos[position_ids[t]] + type[tt[t]]: embed_sum_kernel with the position row given per token (packed
+// variable-length batches, where row t is not at position t mod S); the same sum, in the same order, rounded once
+template <int DT>
+__global__ __launch_bounds__(256) void embed_sum_packed_kernel(const float* __restrict__ word, const float* __restrict__ pos,
+                                                               const float* __restrict__ type, const long long* __restrict__ ids,
+                                                               const long long* __restrict__ tt, const int* __restrict__ pid,
+                                                               unsigned short* __restrict__ z, long long tokens, int H) {
+  const int nch = H >> 3;
+  const long long total = tokens * nch;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long t = i / nch;
+    const int c = (int)(i - t * nch) * 8;
+    const float* w = word + ids[t] * H + c;
+    const float* p = pos + (long long)pid[t] * H + c;
+    const float* y = type + tt[t] * H + c;
+    ushort8_t o;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float4_t a = *(const float4_t*)(w + 4 * h), b = *(const float4_t*)(p + 4 * h), d = *(const float4_t*)(y + 4 * h);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[4 * h + k] = tf_dn<DT>(a[k] + b[k] + d[k]);
+    }
+    *(ushort8_t*)(z + t * H + c) = o;
+  }
+}
+
+extern "C" int dle_embed_sum_packed(const float* word, const float* pos, const float* type, const int64_t* ids,
+                                    const int64_t* token_type, const int32_t* position_ids, void* z, int64_t tokens, int H,
+                                    int dtype, hipStream_t stream) {
+  DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "embed_sum_packed: 16-bit output only");
+  DLE_CHECK_ARG(H > 0 && H % 8 == 0 && tokens >= 0, "embed_sum_packed: bad shape");
+  if (tokens == 0) return 0;
+  DLE_CHECK_ARG(word && pos && type && ids && token_type && position_ids && z, "embed_sum_packed: null pointer");
+  const int grid = tf_grid(tokens * (H / 8), 256);
+  if (dtype == DLE_F16) hipLaunchKernelGGL(embed_sum_packed_kernel<DLE_F16>, dim3(grid), dim3(256), 0, stream, word, pos, type, (const long long*)ids, (const long long*)token_type, (const int*)position_ids, (unsigned short*)z, (long long)tokens, H);
+  else hipLaunchKernelGGL(embed_sum_packed_kernel<DLE_BF16>, dim3(grid), dim3(256), 0, stream, word, pos, type, (const long long*)ids, (const long long*)token_type, (const int*)position_ids, (unsigned short*)z, (long long)tokens, H);
+  DLE_LAUNCH_CHECK();
+  return 0;
+}
+
 // word-embedding gradient: gw[ids[t], :] += dz[t, :]  (fp32 atomics, once per step);
 // type gradient selector sums are done with dle_rows_select_sum below, position gradient with dle_colsum.
 template <int DT>

@@ -1350,6 +1350,20 @@ def embed_sum(word, pos, typ, ids, token_type, seq_len, out_dtype):
     return z
 
 
+def embed_sum_packed(word, pos, typ, ids, token_type, position_ids, out_dtype):
+    """embed_sum for a packed batch: row t takes position row position_ids[t] (int32 [T]) instead of t mod seq_len."""
+    C.require_cuda(word, pos, typ, ids, token_type, position_ids)
+    t = ids.numel()
+    h = word.shape[1]
+    if position_ids.dtype != torch.int32 or position_ids.numel() != t or not position_ids.is_contiguous():
+        raise ValueError("embed_sum_packed: position_ids must be a contiguous int32 tensor with one entry per token")
+    z = torch.empty((t, h), dtype=out_dtype, device=word.device)
+    C.annotate(bytes=float(t) * h * (3 * 4 + 2), tag="T%dxH%d" % (t, h))
+    C.call("dle_embed_sum_packed", C.ptr(word), C.ptr(pos), C.ptr(typ), C.ptr(ids), C.ptr(token_type), C.ptr(position_ids),
+           C.ptr(z), t, h, C.dt(z), C.stream())
+    return z
+
+
 def embed_scatter_add_(grad_word, dz, ids):
     C.require_cuda(grad_word, dz, ids)
     C.call("dle_embed_scatter_add", C.ptr(dz), C.ptr(ids), C.ptr(grad_word), ids.numel(), dz.shape[1], C.dt(dz), C.stream())
@@ -1495,6 +1509,40 @@ def attention_fwd(qkv, mask_add, batch, seq_len, heads, scale, p=0.0, seed=0, of
     C.call("dle_attention_fwd", C.ptr(qkv), C.ptr(mask_add), C.ptr(ctx), C.ptr(stats), C.ptr(mask), batch, seq_len,
            heads, d, float(scale), float(p), int(seed), int(offset), C.ptr(offset_base), C.dt(qkv), C.stream())
     return ctx, stats, mask
+
+
+def attention_varlen_supported(max_seqlen, head_dim):
+    """True when the packed forward attention kernel covers (max_seqlen, head_dim): 64-wide heads, 1 <= max_seqlen <= 1024."""
+    return bool(C.lib().dle_attention_varlen_supported(int(max_seqlen), int(head_dim)))
+
+
+def attention_varlen_launch_count():
+    """Launches of the packed attention kernel by this process so far."""
+    return int(C.lib().dle_attention_varlen_launch_count())
+
+
+def attention_fwd_varlen(qkv, cu_seqlens, max_seqlen, heads, scale, out=None):
+    """context = softmax(q k^T * scale) v per (sequence, head) of a PACKED qkv [T, 3H]: sequence b owns rows
+    cu_seqlens[b] .. cu_seqlens[b + 1] - 1 (int32 device tensor [B + 1], starting at 0; no sequence longer than max_seqlen).
+    Inference only: no dropout, no statistics, the length is the mask.  -> ctx [T, H] (`out` when given)."""
+    C.require_cuda(qkv, cu_seqlens, out)
+    t, h3 = qkv.shape
+    h = h3 // 3
+    d = h // heads
+    if not qkv.is_contiguous() or heads * d * 3 != h3:
+        raise ValueError("attention_fwd_varlen: qkv must be a contiguous [T, 3 * heads * head_dim] tensor")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or not cu_seqlens.is_contiguous():
+        raise ValueError("attention_fwd_varlen: cu_seqlens must be a contiguous int32 tensor [B + 1]")
+    if out is None:
+        out = torch.empty((t, h), dtype=qkv.dtype, device=qkv.device)
+    elif out.shape != (t, h) or out.dtype != qkv.dtype or not out.is_contiguous():
+        raise ValueError("attention_fwd_varlen: out must be a contiguous [T, H] tensor of qkv's dtype")
+    b = cu_seqlens.numel() - 1
+    # (upper bound of the work: every sequence at max_seqlen; the real figure needs the lengths on the host)
+    C.annotate(flops=6.0 * t * max_seqlen * h, bytes=float(t) * h * 2 * 4, tag="T%dxB%dxh%dxS%dxd%d" % (t, b, heads, max_seqlen, d))
+    C.call("dle_attention_fwd_varlen", C.ptr(qkv), C.ptr(cu_seqlens), C.ptr(out), b, int(max_seqlen), t, heads, d, float(scale),
+           C.dt(qkv), C.stream())
+    return out
 
 
 def attention_bwd(qkv, dctx, mask_add, stats, batch, seq_len, heads, scale, p=0.0, seed=0, offset=0, offset_base=None,

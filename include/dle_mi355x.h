@@ -523,6 +523,12 @@ int dle_layernorm_bwd(const void* dy, const void* z, const float* mean, const fl
 /* z[t] = word[ids[t]] + pos[t mod S] + type[token_type[t]]  (fp32 tables -> 16-bit) */
 int dle_embed_sum(const float* word, const float* pos, const float* type, const int64_t* ids,
                   const int64_t* token_type, void* z, int64_t tokens, int S, int H, int dtype, hipStream_t stream);
+/* The same with the position row given per token, z[t] = word[ids[t]] + pos[position_ids[t]] + type[token_type[t]]: the
+ * embedding sum of a PACKED batch (sequences back to back, no padding rows), where row t is not at position t mod S.  Same
+ * arithmetic and rounding as dle_embed_sum.  position_ids: int32 [tokens]. */
+int dle_embed_sum_packed(const float* word, const float* pos, const float* type, const int64_t* ids,
+                         const int64_t* token_type, const int32_t* position_ids, void* z, int64_t tokens, int H, int dtype,
+                         hipStream_t stream);
 /* grad_word[ids[t], :] += dz[t, :] (fp32) */
 int dle_embed_scatter_add(const void* dz, const int64_t* ids, float* grad_word, int64_t tokens, int H, int dtype,
                           hipStream_t stream);
@@ -611,6 +617,25 @@ int dle_attention_bwd(const void* qkv, const void* dctx, const float* mask_add, 
 int dle_attention_bwd_keep(const void* qkv, const void* dctx, const float* mask_add, const float* stats, const void* keep_mask,
                            void* dqkv, float* colsum_partial, int B, int S, int heads, int head_dim, float scale, float p,
                            uint64_t seed, uint64_t offset, const uint64_t* offset_base, int dtype, hipStream_t stream);
+
+/* ---- packed (variable-length) forward attention, inference only: BertSelfAttention.forward under model.eval()
+ * (LanguageModeling/BERT/modeling.py:340-384) on the real rows of a batch that extract_features.py:262-294 pads to
+ * [B, max_seq_length].  qkv [T, 3H] (column layout of dle_attention_fwd) holds the sequences back to back; sequence b owns rows
+ * cu_seqlens[b] .. cu_seqlens[b + 1] - 1 (cu_seqlens: DEVICE int32 [B + 1], cu_seqlens[0] = 0, no sequence longer than
+ * max_seqlen); ctx [T, H].  No dropout, no statistics output, no mask_add: the length is the mask, and a sequence's rows get
+ * the bits dle_attention_fwd(p = 0) gives them in a padded batch under a 0 / -10000 mask.  One workgroup per (sequence, head,
+ * 128-query block), keys streamed through LDS in 128-key blocks; max_seqlen need not be a multiple of 128.
+ * Rows of the next sequence that a 128-row tile covers are read as zero (the buffer resource ends with the sequence), so a
+ * sequence's result does not depend on its neighbours' values, Inf and NaN included.
+ * Offsets into qkv are 32-bit and a tile reaches up to 127 rows past a sequence's last: (total_tokens + 127) * 3H * 2 >= 2^32
+ * bytes is an error (-1, dle_last_error), as is anything outside
+ * dle_attention_varlen_supported (1: head_dim == 64 and 1 <= max_seqlen <= 1024).  Lengths are clamped to [0, max_seqlen] and
+ * rows to total_tokens inside the kernel: a wrong table gives wrong answers but reaches no memory outside qkv / ctx.
+ * dle_attention_varlen_launch_count(): launches by this process so far (tests assert which path ran). */
+int dle_attention_varlen_supported(int max_seqlen, int head_dim);
+int dle_attention_fwd_varlen(const void* qkv, const int32_t* cu_seqlens, void* ctx, int B, int max_seqlen,
+                             int64_t total_tokens, int heads, int head_dim, float scale, int dtype, hipStream_t stream);
+uint64_t dle_attention_varlen_launch_count(void);
 
 /* ---- torch.optim.Adam over a tensor table (csrc/multi_tensor.hip): GradScaler.unscale_ + clip_grad_norm_ + Adam.step of
  * SpeechSynthesis/Tacotron2/train.py:400-401,487-497 in one pass.  lists: g, p, exp_avg, exp_avg_sq (all fp32).
