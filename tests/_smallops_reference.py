@@ -19,7 +19,12 @@ these float64 statements only, starting from 2 u each (the one-ulp figure usuall
 the largest recorded ratio of what they enter is at most 0.5.  With 2 u that run recorded (the full table is in the GPU test's
 docstring):
     C_LOG   xent loss 0.083 (narrow), 0.076 (wide)                                            kept at 2
-    C_RCP   act_bwd gelu, the fp32 part of the bar (the store's half ulp taken off) 0.297       kept at 2
+    C_RCP   act_bwd gelu, the fp32 part of the bar (the store's half ulp taken off) 0.297       kept at 2 by that run; now 3:
+            the run of tests/test_gpu_tacotron2_reference.py on an MI355X recorded, on the elements of the LSTM cell state whose bar
+            is at least half C_EXP / C_RCP (fast_tanh near 0, where its error is the absolute (C_EXP / 2 + 1 + C_RCP) u and the
+            reciprocal has the largest share), 0.505 (fp16) and 0.493 (bf16) with 2 u; 3 u is the smallest integer that brings them
+            to 0.5 or below: 0.410 and 0.400 (C_EXP = 3 instead: 0.450 and 0.439).  The figures in this module's and in the smallops
+            tests' docstrings were recorded with C_RCP = 2 u; the constant enters fast_tanh_delta only, i.e. the fp32 part of act_bwd gelu.
     C_EXP   BCE loss 0.093, BCE fp32 gradient 0.420, act_bwd gelu 0.297, xent loss as above   kept at 2
             xent fp32 gradient 0.563 (narrow), 0.532 (wide): above 0.5, but not through C_EXP -- the largest ratios sit at
             elements with p << s / classes, where g = -(s / classes) gs and the bar is 4 u |g| of plain roundings; the fp32
@@ -35,7 +40,7 @@ import torch
 
 F64, F32, F16, BF16, U8 = torch.float64, torch.float32, torch.float16, torch.bfloat16, torch.uint8
 U = 2.0 ** -24
-C_EXP, C_LOG, C_RCP = 2.0, 2.0, 2.0
+C_EXP, C_LOG, C_RCP = 2.0, 2.0, 3.0
 TINY = 2.0 ** -126                  # below it fp32 errors are absolute (subnormal spacing, or a flush to zero)
 MANT = {F16: 10, BF16: 7, F32: 23}
 EMIN = {F16: -14, BF16: -126, F32: -126}
