@@ -1,10 +1,11 @@
-"""Classify one image with ResNet-50 on the MI355X: the interface of the reference's classify.py
-(Classification/ConvNets/classify.py:56-76,119-144) on convnets.infer.ResNet50Classifier.
+"""Classify one image with ResNet-50 or SE-ResNeXt101-32x4d on the MI355X: the interface of the reference's classify.py
+(Classification/ConvNets/classify.py:56-76,119-144) on convnets.infer.ResNet50Classifier / ResNeXtClassifier.
 
     python -m deeplearningexamples_amd.convnets.classify --image IMG --pretrained-from-file WEIGHTS [--amp-dtype fp16]
 
---arch, --image-size, --precision, --cpu, --image and the model's --pretrained-from-file are the reference's flags.  Only resnet50
-is built; FP32 and --cpu are parsed and rejected with a message.  --amp-dtype picks the 16-bit type (the reference's autocast is
+--arch, --image-size, --precision, --cpu, --image and the model's --pretrained-from-file are the reference's flags.  resnet50 and
+se-resnext101-32x4d are built (plain resnext101-32x4d is evaluated through convnets.main --evaluate only); FP32 and --cpu are
+parsed and rejected with a message.  --amp-dtype picks the 16-bit type (the reference's autocast is
 fp16).  The image is decoded with PIL when it is installed; otherwise --image takes a uint8 HWC (or HW) array saved with
 numpy.save, the pre-decoded form convnets/dataloaders.py reads.  Resize to image-size + 32, centre crop and mean / std
 normalisation run on the device.  Class names come from --synset-mapping FILE (a JSON list, the layout of the reference's
@@ -18,12 +19,13 @@ import torch
 
 ARCHS = ("resnet50", "resnext101-32x4d", "se-resnext101-32x4d", "efficientnet-b0", "efficientnet-b4", "efficientnet-widese-b0",
          "efficientnet-widese-b4", "efficientnet-quant-b0", "efficientnet-quant-b4")
+BUILT = ("resnet50", "se-resnext101-32x4d")
 
 
 def add_parser_arguments(parser):
     parser.add_argument("--image-size", default=224, type=int)
     parser.add_argument("--arch", "-a", metavar="ARCH", default="resnet50", choices=ARCHS,
-                        help="model architecture: " + " | ".join(ARCHS) + " (default: resnet50; the only one built)")
+                        help="model architecture: " + " | ".join(ARCHS) + " (default: resnet50; built: " + ", ".join(BUILT) + ")")
     parser.add_argument("--precision", metavar="PREC", default="AMP", choices=["AMP", "FP32"])
     parser.add_argument("--cpu", action="store_true", help="perform inference on CPU (not built)")
     parser.add_argument("--image", metavar="<path>", help="path to classified image")
@@ -35,8 +37,11 @@ def add_parser_arguments(parser):
 
 
 def reject_unbuilt(args):
-    if args.arch != "resnet50":
-        raise SystemExit("--arch %s: only resnet50 is built on this path" % args.arch)
+    if args.arch == "resnext101-32x4d":
+        raise SystemExit("--arch resnext101-32x4d: classify serves resnet50 and se-resnext101-32x4d; evaluate this one with "
+                         "convnets.main --arch resnext101-32x4d --evaluate")
+    if args.arch not in BUILT:
+        raise SystemExit("--arch %s: only resnet50 and se-resnext101-32x4d are built on this path" % args.arch)
     if args.cpu:
         raise SystemExit("--cpu: the kernels run on the MI355X only; there is no CPU path")
     if args.precision != "AMP":
@@ -90,12 +95,18 @@ def format_top5(path, probs, indices, names=None):
 def main(argv=None):
     args = add_parser_arguments(argparse.ArgumentParser(description="ResNet-50 image classification on MI355X")).parse_args(argv)
     reject_unbuilt(args)
-    from .infer import ResNet50Classifier
+    from .infer import ResNet50Classifier, ResNeXtClassifier
     from .resnet import ResNet50
+    from .resnext import build as build_resnext
     device = torch.device("cuda", 0)
     dtype = torch.bfloat16 if args.amp_dtype == "bf16" else torch.float16
     names = json.load(open(args.synset_mapping)) if args.synset_mapping else None
-    if args.pretrained_from_file:
+    if args.arch != "resnet50":
+        if args.pretrained_from_file:
+            clf = ResNeXtClassifier.from_checkpoint(args.pretrained_from_file, dtype=dtype, device=device)
+        else:
+            clf = ResNeXtClassifier(build_resnext(args.arch, device=device), dtype=dtype)
+    elif args.pretrained_from_file:
         clf = ResNet50Classifier.from_checkpoint(args.pretrained_from_file, dtype=dtype, device=device)
     else:
         clf = ResNet50Classifier(ResNet50(device=device), dtype=dtype)          # (random weights, as the reference without a file)

@@ -12,12 +12,16 @@ One stream: image layout pass -> stem convolution -> affine + ReLU + max pooling
 downsample: affine; conv3: affine + residual + ReLU) -> average pooling -> fc.  graphs=True keeps one captured graph (a single
 chain) and one static input buffer per input shape; the logits of a call then live in a buffer the classifier owns: copy them
 before the next call at that shape.
+
+ResNeXtClassifier (below) serves ResNeXt101-32x4d and SE-ResNeXt101-32x4d on the same stem, 1x1 units, pooling and fc, with the
+grouped 3x3 kernel and the squeeze-and-excitation launches in the block.
 """
 import torch
 
 from .. import functional as F
 from ..utils.graph import GraphedStep
-from .resnet import ResNet50
+from .resnet import ConvBN, ResNet50
+from .resnext import CARDINALITY, ResNeXt101, state_has_se
 
 # Units routed back to the two-launch form (convolution, then the stand-alone BatchNorm-apply): (kernel size, stride, C, Ko).
 # The place to put a unit whose fused launch measures slower than the pair; tools/rn50_infer_perf.py times whole networks only, so
@@ -152,9 +156,9 @@ class ResNet50Classifier:
     def logits(self, images):
         """images: fp32 (or uint8, normalised on the way in) NCHW, contiguous or channels_last -> fp32 logits [N, classes]."""
         if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError("ResNet50Classifier: images must be [N, 3, H, W] (got %s)" % (tuple(images.shape),))
+            raise ValueError("%s: images must be [N, 3, H, W] (got %s)" % (type(self).__name__, tuple(images.shape)))
         if images.dtype not in (torch.float32, torch.uint8):
-            raise ValueError("ResNet50Classifier: fp32 or uint8 images (got %s)" % images.dtype)
+            raise ValueError("%s: fp32 or uint8 images (got %s)" % (type(self).__name__, images.dtype))
         if images.device != self.dev:
             images = images.to(self.dev)
         if not images.is_contiguous():
@@ -172,3 +176,84 @@ class ResNet50Classifier:
         """-> (softmax probabilities [N, classes] fp32, the indices [N, topk] of the most probable classes, most probable first)."""
         probs = torch.softmax(self.logits(images), dim=1)
         return probs, torch.topk(probs, min(topk, probs.shape[1]), dim=1).indices
+
+
+class _Block:
+    """One (SE-)ResNeXt bottleneck as the kernels read it."""
+    __slots__ = ("u1", "u3", "ud", "w2", "scale2", "shift2", "stride", "se")
+
+
+class ResNeXtClassifier(ResNet50Classifier):
+    """ResNeXt101-32x4d / SE-ResNeXt101-32x4d inference (models/resnet.py:412-458): ResNet50Classifier's stem, 1x1 units, pooling and
+    fc around the grouped 3x3 kernel (functional.conv2d_grouped_fwd_affine) and, for the SE variant, the two squeeze-and-excitation
+    launches.  Per block: downsample (affine) on the first block of a stage, conv1 (affine + ReLU), the grouped conv2 (affine +
+    ReLU), then conv3 with the residual and the ReLU in its epilogue -- or, with SE, conv3 (affine only), se_gate, se_apply
+    (gate, residual, ReLU).  At 224 x 224: 33 x 3 + 4 convolution launches and at most 66 SE launches between the stem and the
+    average pooling.  Grouped weights are packed [Ko, 3, 3, Cg] once here; SE weights stay fp32."""
+
+    def __init__(self, model, dtype=torch.bfloat16, device=None, graphs=False):
+        """model: a ResNeXt101 (left untouched) or a state dict of either architecture (any device; `module.` prefixes allowed; the
+        SE variant is recognised by its squeeze weights)."""
+        if dtype == torch.float32:
+            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
+                             "recipes are not built)")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("ResNeXtClassifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        if not isinstance(model, ResNeXt101):
+            state = state_from_checkpoint(model)
+            dev = torch.device(device if device is not None else "cuda")
+            module = ResNeXt101(num_classes=state["fc.weight"].shape[0], se=state_has_se(state), device=dev)
+            module.load_state_dict(state)
+            model = module
+        self.dev = model.fc.weight.device
+        self.dtype, self.graphs = dtype, bool(graphs)
+        self.num_classes = model.fc.weight.shape[0]
+        self.se = model.se
+        with torch.no_grad():
+            self.stem = self._unit(ConvBN(model.conv1, model.bn1, "conv1", "bn1", relu=True))
+            self.stem_w2 = F.stem_pack_weight(model.conv1.weight.data, dtype)
+            self.blocks = [self._block(blk) for blk in model.bottlenecks()]
+            self.fc_w16 = F.cast(model.fc.weight.data, dtype)
+            self.fc_bias = model.fc.bias.data.float().clone()
+        self._mean_std = None
+        self._graphs = {}
+
+    def _block(self, blk):
+        b = _Block()
+        b.u1 = self._unit(ConvBN(blk.conv1, blk.bn1, "conv1", "bn1", relu=True))
+        # conv3 carries the residual add and the last ReLU in its epilogue; with SE both move to se_apply
+        b.u3 = self._unit(ConvBN(blk.conv3, blk.bn3, "conv3", "bn3", relu=blk.squeeze is None))
+        b.ud = None
+        if blk.downsample is not None:
+            b.ud = self._unit(ConvBN(blk.downsample[0], blk.downsample[1], "downsample.0", "downsample.1", relu=False))
+        b.w2 = F.pack_grouped_weight(blk.conv2.weight.data, self.dtype)
+        b.scale2, b.shift2 = fold_bn(blk.bn2.weight.data, blk.bn2.bias.data, blk.bn2.running_mean, blk.bn2.running_var, blk.bn2.eps)
+        b.stride = blk.conv2.stride[0]
+        b.se = None
+        if blk.squeeze is not None:
+            sq, ex = blk.squeeze.squeeze, blk.squeeze.expand
+            b.se = tuple(t.data.float().contiguous().clone() for t in (sq.weight, sq.bias, ex.weight, ex.bias))
+        return b
+
+    def _forward(self, images):
+        h = self._stem(images)
+        for b in self.blocks:
+            res = self._run(b.ud, h) if b.ud is not None else h
+            t = self._run(b.u1, h)
+            t = F.conv2d_grouped_fwd_affine(t, b.w2, b.scale2, b.shift2, CARDINALITY, b.stride, relu=True)
+            if b.se is None:
+                h = self._run(b.u3, t, residual=res)
+            else:
+                t = self._run(b.u3, t)
+                h = F.se_apply(t, F.se_gate(t, *b.se), residual=res, relu=True)
+        pooled = F.avgpool_fwd(h)
+        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
+                      out_dtype=torch.float32, bias=self.fc_bias)
+
+    def eval_step(self, images, target):
+        """-> (loss [1] (plain cross entropy, like ResNetTrainer.eval_step), fp32 logits)."""
+        logits = self.logits(images)
+        if target.device != self.dev:
+            target = target.to(self.dev)
+        loss, _ = F.softmax_xent(logits, target, smoothing=0.0)
+        return loss, logits

@@ -8,7 +8,9 @@ Launch one process per GPU:
     python -m torch.distributed.run --nproc-per-node 8 -m deeplearningexamples_amd.convnets.main \
         --arch resnet50 --data-backend synthetic --batch-size 256 --amp --epochs 1 --prof 100 /data/imagenet
 Flags of the reference that select machinery outside this path (DALI, TorchScript, RMSprop, other architectures) are
-parsed and rejected with a message instead of an argparse error.
+parsed and rejected with a message instead of an argparse error.  --arch resnext101-32x4d / se-resnext101-32x4d are inference-only:
+with --evaluate they run the validation loop on convnets.infer.ResNeXtClassifier (no trainer is built), without it they exit with a
+message.
 """
 import argparse
 import os
@@ -23,6 +25,7 @@ from ..utils.dist import init_from_env, is_main_process
 from .dataloaders import MixUpWrapper, get_pytorch_train_loader, get_pytorch_val_loader, get_synthetic_loader
 from .engine import ResNetTrainer, lr_cosine_policy, lr_linear_policy, lr_step_policy
 from .resnet import ResNet50
+from .resnext import ARCHS as RESNEXT_ARCHS
 
 
 def add_parser_arguments(parser):
@@ -31,7 +34,8 @@ def add_parser_arguments(parser):
     p.add_argument("--data-backend", default="synthetic", choices=["pytorch", "synthetic", "dali-gpu", "dali-cpu"],
                    help="synthetic (dataloaders.py:520-577) or pytorch (ImageFolder + PrefetchedWrapper, :354-517); DALI is not built")
     p.add_argument("--interpolation", default="bilinear")
-    p.add_argument("--arch", "-a", default="resnet50", choices=["resnet50"])
+    p.add_argument("--arch", "-a", default="resnet50", choices=["resnet50"] + list(RESNEXT_ARCHS),
+                   help="resnet50 trains and evaluates; the ResNeXt architectures are inference-only (--evaluate)")
     p.add_argument("-j", "--workers", default=5, type=int)
     p.add_argument("--prefetch", default=2, type=int)
     p.add_argument("--epochs", default=90, type=int)
@@ -87,6 +91,8 @@ def add_parser_arguments(parser):
 
 
 def _reject_unbuilt(args):
+    if args.arch in RESNEXT_ARCHS and not args.evaluate:
+        raise SystemExit("--arch %s is inference-only here: pass --evaluate (resnet50 is the architecture that trains)" % args.arch)
     if args.data_backend.startswith("dali"):
         raise SystemExit("--data-backend %s: DALI is not part of this path; use pytorch or synthetic" % args.data_backend)
     if args.optimizer != "sgd":
@@ -193,9 +199,47 @@ def train_loop(trainer, args, lr_policy, train_loader, train_len, val_loader, st
     return iters, time.time() - t0, best_prec1
 
 
+def evaluate_resnext(args):
+    """--arch (se-)resnext101-32x4d --evaluate: the model (random, or --pretrained-from-file / --resume through
+    state_from_checkpoint), the classifier of convnets/infer.py and the `validate` loop on its eval_step.  No trainer."""
+    from . import resnext
+    from .infer import ResNeXtClassifier, state_from_checkpoint
+    rank, world, local = init_from_env()
+    device = torch.device("cuda", local)
+    if args.seed is not None:
+        torch.manual_seed(args.seed + local)
+        np.random.seed(args.seed + local)
+    os.makedirs(args.workspace, exist_ok=True)
+    if is_main_process():
+        dllogger.init([dllogger.JSONStreamBackend(dllogger.Verbosity.VERBOSE, os.path.join(args.workspace, args.raport_file)),
+                       dllogger.StdOutBackend(dllogger.Verbosity.DEFAULT)])
+        dllogger.log(step="PARAMETER", data=vars(args))
+    model = resnext.build(args.arch, num_classes=args.num_classes, last_bn_0_init=args.last_bn_0_init, device=device)
+    path = args.pretrained_from_file or args.resume
+    if path:
+        if not os.path.isfile(path):
+            raise SystemExit("=> no checkpoint found at '%s'" % path)
+        model.load_state_dict(state_from_checkpoint(torch.load(path, map_location=device, weights_only=False)))
+    dtype = torch.bfloat16 if args.amp_dtype == "bf16" else torch.float16
+    clf = ResNeXtClassifier(model, dtype=dtype)
+    get_val = get_synthetic_loader if args.data_backend == "synthetic" else get_pytorch_val_loader
+    val_loader, _ = get_val(args.data, args.image_size, args.batch_size, args.num_classes, workers=args.workers,
+                            memory_format=args.memory_format, prefetch_factor=args.prefetch, device=device, rank=rank, world=world,
+                            seed=args.seed, steps_per_epoch=args.steps_per_epoch, interpolation=args.interpolation)
+    best = validate(None, val_loader, args, 0, world, eval_step=clf.eval_step)
+    torch.cuda.synchronize()
+    if is_main_process():
+        dllogger.log(step=tuple(), data={"iterations": 0, "best_prec1": best})
+        dllogger.flush()
+    print("Experiment ended")
+    return clf
+
+
 def main(argv=None):
     args = add_parser_arguments(argparse.ArgumentParser(description="ResNet-50 training on MI355X")).parse_args(argv)
     _reject_unbuilt(args)
+    if args.arch in RESNEXT_ARCHS:
+        return evaluate_resnext(args)
     rank, world, local = init_from_env()
     device = torch.device("cuda", local)
     if args.seed is not None:

@@ -665,6 +665,87 @@ def conv2d_fwd_affine(x, w, scale, shift, stride=1, pad=0, residual=None, relu=T
     return out
 
 
+def pack_grouped_weight(w, dtype):
+    """torch's grouped OIHW weight [Ko, Cg, 3, 3] (any device / float dtype / memory format) -> the [Ko, 3, 3, Cg] 16-bit tensor
+    conv2d_grouped_fwd_affine reads (one rounding per element)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("pack_grouped_weight: expected a [Ko, Cg, 3, 3] weight (got %s)" % (tuple(w.shape),))
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("pack_grouped_weight: dtype must be torch.float16 or torch.bfloat16")
+    return w.detach().permute(0, 2, 3, 1).to(dtype).contiguous()
+
+
+def conv2d_grouped_fwd_affine(x, w, scale, shift, groups, stride=1, relu=True, out=None):
+    """Grouped 3x3 / pad 1 inference unit in one launch: y = relu?(scale[ko] * conv_g(x, w) + shift[ko]) on the fp32 accumulator,
+    rounded once.  x [N,H,W,C], w [Ko,3,3,C/groups] (pack_grouped_weight; 16-bit, contiguous), scale / shift fp32 [Ko]
+    -> y [N,P,Q,Ko].  C == Ko, C % 64 == 0, C / groups in {4, 8, 16, 32}, stride 1 or 2: anything else raises ValueError."""
+    C.require_cuda(x, w, scale, shift, out)
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError("conv2d_grouped_fwd_affine: x must be [N,H,W,C] and w [Ko,3,3,Cg]")
+    n, h, wd, c = x.shape
+    ko, r, s, cg = w.shape
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("conv2d_grouped_fwd_affine: 16-bit activations and weights only (got %s)" % x.dtype)
+    if (r, s) != (3, 3) or groups < 1 or cg * groups != c or not x.is_contiguous() or not w.is_contiguous() or x.dtype != w.dtype:
+        raise ValueError("conv2d_grouped_fwd_affine: x must be NHWC-contiguous and w [Ko,3,3,C/groups]-contiguous of x's dtype")
+    if stride < 1:
+        raise ValueError("conv2d_grouped_fwd_affine: stride 1 or 2")
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.numel() != ko or not t.is_contiguous():
+            raise ValueError("conv2d_grouped_fwd_affine: scale / shift must be contiguous fp32 [Ko]")
+    p, q = _conv_out(h, wd, 3, 3, stride, 1)
+    if out is None:
+        out = torch.empty((n, p, q, ko), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (n, p, q, ko) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("conv2d_grouped_fwd_affine: out must be a contiguous [N,P,Q,Ko] tensor of x's dtype")
+    C.annotate(flops=2.0 * n * p * q * ko * 9 * cg, tag="grouped %dx%dx%dx%d g%d s%d" % (n, h, wd, c, groups, stride),
+               bytes=float(x.numel() + w.numel() + out.numel()) * 2)
+    C.call("dle_conv2d_grouped_fwd_affine", C.ptr(x), C.ptr(w), C.ptr(out), C.ptr(scale), C.ptr(shift), n, h, wd, c, ko, groups,
+           stride, C.dt(x), int(bool(relu)), C.stream())
+    return out
+
+
+def se_gate(t, w1, b1, w2, b2, out=None):
+    """Squeeze-and-excitation gate: sigmoid(w2 @ relu(w1 @ mean_hw(t) + b1) + b2) per image, in fp32.  t [N,H,W,C] or [N,HW,C]
+    16-bit contiguous; w1 [S,C], b1 [S], w2 [C,S], b2 [C] contiguous fp32 (S <= 64) -> gate [N,C] fp32."""
+    C.require_cuda(t, w1, b1, w2, b2, out)
+    if t.dim() not in (3, 4) or not t.is_contiguous() or t.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("se_gate: t must be a contiguous 16-bit [N,H,W,C] or [N,HW,C] tensor")
+    n, c = t.shape[0], t.shape[-1]
+    hw = t.numel() // max(n * c, 1)
+    s = w1.shape[0]
+    for v, shape in ((w1, (s, c)), (b1, (s,)), (w2, (c, s)), (b2, (c,))):
+        if v.dtype != torch.float32 or tuple(v.shape) != shape or not v.is_contiguous():
+            raise ValueError("se_gate: weights must be contiguous fp32 w1 [S,C], b1 [S], w2 [C,S], b2 [C]")
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=t.device)
+    elif tuple(out.shape) != (n, c) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("se_gate: out must be a contiguous fp32 [N,C] tensor")
+    C.call("dle_se_gate", C.ptr(t), C.ptr(w1), C.ptr(b1), C.ptr(w2), C.ptr(b2), C.ptr(out), n, hw, c, s, C.dt(t), C.stream())
+    return out
+
+
+def se_apply(t, gate, residual=None, relu=True, out=None):
+    """y = relu?(t * gate[n, c] + residual) in fp32, rounded once.  t, residual (or None) 16-bit contiguous [N,H,W,C] / [N,HW,C],
+    gate fp32 [N,C] -> y of t's shape and dtype."""
+    C.require_cuda(t, gate, residual, out)
+    if t.dim() not in (3, 4) or not t.is_contiguous() or t.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("se_apply: t must be a contiguous 16-bit [N,H,W,C] or [N,HW,C] tensor")
+    n, c = t.shape[0], t.shape[-1]
+    hw = t.numel() // max(n * c, 1)
+    if gate.dtype != torch.float32 or tuple(gate.shape) != (n, c) or not gate.is_contiguous():
+        raise ValueError("se_apply: gate must be a contiguous fp32 [N,C] tensor")
+    if residual is not None and (residual.shape != t.shape or residual.dtype != t.dtype or not residual.is_contiguous()):
+        raise ValueError("se_apply: residual must be a contiguous tensor of t's shape and dtype")
+    if out is None:
+        out = torch.empty_like(t)
+    elif out.shape != t.shape or out.dtype != t.dtype or not out.is_contiguous():
+        raise ValueError("se_apply: out must be a contiguous tensor of t's shape and dtype")
+    C.annotate(tag="se_apply %dx%dx%d" % (n, hw, c), bytes=float(t.numel() * (3 if residual is not None else 2)) * 2)
+    C.call("dle_se_apply", C.ptr(t), C.ptr(gate), C.ptr(residual), C.ptr(out), n, hw, c, C.dt(t), int(bool(relu)), C.stream())
+    return out
+
+
 def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, addend=None, out=None):
     """dy [N,P,Q,Ko], w [Ko,R,S,C] -> dx [N,H,W,C] (+ addend)."""
     C.require_cuda(dy, w, addend, out)

@@ -206,6 +206,32 @@ int dle_conv2d_fwd_affine(const void* x, const void* w, void* y, const float* sc
                           const void* residual, int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad,
                           int dtype, int relu, hipStream_t stream);
 int64_t dle_conv3x3_affine_launch_count(void);
+/* Inference, grouped: the 3x3 / pad 1 / stride 1 or 2 convolution with `groups` groups (conv2 of the ResNeXt bottleneck) with the
+ * evaluation-mode BatchNorm and the ReLU in its epilogue.  Replaces, under model.eval(), the cuDNN grouped convolution behind
+ *   Classification/ConvNets/image_classification/models/resnet.py:107-175 (Bottleneck with cardinality 32: nn.Conv2d(groups=32)
+ *   -> bn2 -> relu), models/resnet.py:412-458 (resnext101-32x4d, se-resnext101-32x4d)
+ *   y[n,p,q,ko] = round16( relu?( fmaf(scale[ko], acc, shift[ko]) ) ),   P = (H-1)/stride + 1
+ * x [N,H,W,C] NHWC 16-bit; w [Ko][3][3][Cg] 16-bit = torch's grouped OIHW weight [Ko, Cg, 3, 3] permuted (0,2,3,1); acc: the fp32
+ * MFMA accumulator over the UNMODIFIED 16-bit weights of ko's group only; round-to-nearest-even, once; no residual operand.
+ * Envelope: C == Ko, C % 64 == 0, Cg = C / groups in {4, 8, 16, 32}, stride in {1, 2}, any H, W >= 1, each tensor < 4 GiB, every
+ * operand 16-byte aligned; anything else is an argument error (-1), never a fallback.  No allocation, no synchronisation (graph
+ * capturable); no dynamic LDS (csrc/conv_grouped.hip). */
+int dle_conv2d_grouped_fwd_affine(const void* x, const void* w, void* y, const float* scale, const float* shift,
+                                  int N, int H, int W, int C, int Ko, int groups, int stride,
+                                  int dtype, int relu, hipStream_t stream);
+/* Inference, squeeze-and-excitation (csrc/se.hip).  Replaces, under model.eval(),
+ *   models/common.py:146-164 (SqueezeAndExcitation: mean over H x W -> nn.Linear(C, S) -> ReLU -> nn.Linear(S, C) -> sigmoid),
+ *   models/resnet.py:165-173 (`out = torch.addcmul(residual, out, self.squeeze(out))`, relu)
+ * se_gate:  gate[n,c] = sigmoid(b2[c] + sum_s w2[c,s] * relu(b1[s] + sum_c' w1[s,c'] * mean_hw t[n,hw,c']))
+ *           t [N,HW,C] 16-bit (16-byte aligned), the mean in fp32; w1 [S,C], b1 [S], w2 [C,S], b2 [C], gate [N,C] fp32 -- both
+ *           products in fp32 on fp32 weights (the reference's autocast runs them in fp16).  S <= 64, C % 8 == 0.
+ * se_apply: y = round16( relu?( fmaf(float(t), gate[n,c], float(residual)) ) ), residual 16-bit [N,HW,C] or NULL, 16-byte loads and
+ *           stores (every operand 16-byte aligned, C % 8 == 0).
+ * No allocation, no synchronisation. */
+int dle_se_gate(const void* t, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                int N, int HW, int C, int S, int dtype, hipStream_t stream);
+int dle_se_apply(const void* t, const float* gate, const void* residual, void* y,
+                 int64_t N, int HW, int C, int dtype, int relu, hipStream_t stream);
 int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int R, int S,
                      int stride, int pad, int dtype, int splitk, int accumulate, void* workspace,
                      int64_t workspace_bytes, hipStream_t stream);
