@@ -235,6 +235,8 @@ _SIGS = {
                                     c_int, c_int, c_void_p]),
     "dle_t2_frame_infer": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 7 + [c_int, c_float, c_int, c_i64, c_void_p,
                                    c_void_p, c_void_p, c_i64, c_u64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dle_conv1d_lrelu_fwd": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float, c_float, c_int, c_void_p]),
+    "dle_hfg_post_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float, c_int, c_void_p]),
 }
 
 _lib = None

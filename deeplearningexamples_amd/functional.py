@@ -1661,3 +1661,99 @@ def unpack_dropout_mask(mask, shape):
     """Bit-packed keep mask -> bool tensor of `shape` (bit k of byte i <-> flat element 8 i + k)."""
     bits = (mask.to(torch.int32).unsqueeze(1) >> torch.arange(8, device=mask.device, dtype=torch.int32)) & 1
     return bits.reshape(shape).bool()
+
+
+# ------------------------------------------------------------------ HiFi-GAN generator (csrc/hifigan.hip)
+def fold_weight_norm(v, g):
+    """torch.nn.utils.weight_norm (dim = 0) folded: w = g * v / ||v|| in fp32, the norm over every dimension but 0 (the output
+    channel of a Conv1d, the INPUT channel of a ConvTranspose1d).  Host packing: any device, exact fp32 arithmetic of torch."""
+    v, g = v.detach().float(), g.detach().float()
+    if v.dim() < 2 or g.shape[0] != v.shape[0] or g.numel() != v.shape[0]:
+        raise ValueError("fold_weight_norm: v [O, ...] and g [O, 1, ...] expected (got %s, %s)" % (tuple(v.shape), tuple(g.shape)))
+    # torch._weight_norm is the function behind torch.nn.utils.weight_norm / remove_weight_norm: v * (g / ||v||), the norm as
+    # torch sums it -- a fold written out here differs from a checkpoint saved after remove_weight_norm in the last bit
+    return torch._weight_norm(v.contiguous(), g.reshape((v.shape[0],) + (1,) * (v.dim() - 1)).contiguous(), 0)
+
+
+def pack_conv1d_weight(w, dtype):
+    """torch's Conv1d weight [Ko, C, ksize] -> the [Ko, ksize, C] 16-bit tensor conv1d_lrelu_fwd reads (one rounding per element)."""
+    if w.dim() != 3:
+        raise ValueError("pack_conv1d_weight: expected a [Ko, C, ksize] weight (got %s)" % (tuple(w.shape),))
+    if dtype not in (torch.float16, torch.bfloat16, torch.float64):
+        raise ValueError("pack_conv1d_weight: dtype must be torch.float16 or torch.bfloat16")
+    return w.detach().permute(0, 2, 1).to(dtype).contiguous()
+
+
+def pack_upsample_weight(w, stride, dtype):
+    """ConvTranspose1d(Cin, Cout, k, stride u, padding (k - u) // 2) weight [Cin, Cout, k] -> the [u * Cout, 3, Cin] weight of the
+    3-tap, dilation-1 "same" Conv1d that computes it:  packed[p * Cout + ko, j, c] = w[c, ko, (1 - j) * u + p + (k - u) // 2]
+    where that index lies in [0, k), 0 elsewhere.  The convolution's [B, T, u * Cout] output is, as it lies in memory, the
+    [B, T * u, Cout] tensor of the transposed convolution; its bias is the layer's repeated u times.  k - u even, k <= 2 u.
+    dtype torch.float64 keeps the values unrounded (tests)."""
+    if w.dim() != 3:
+        raise ValueError("pack_upsample_weight: expected a [Cin, Cout, k] weight (got %s)" % (tuple(w.shape),))
+    cin, cout, k = w.shape
+    u = int(stride)
+    if u < 1 or (k - u) % 2 or k > 2 * u or k < u:
+        raise ValueError("pack_upsample_weight: needs k - stride even and stride <= k <= 2 stride (got k = %d, stride = %d)" % (k, u))
+    if dtype not in (torch.float16, torch.bfloat16, torch.float64):
+        raise ValueError("pack_upsample_weight: dtype must be torch.float16 or torch.bfloat16")
+    pad = (k - u) // 2
+    src = w.detach().to(torch.float64 if dtype == torch.float64 else torch.float32)
+    packed = torch.zeros((u, cout, 3, cin), dtype=src.dtype, device=w.device)
+    for j in range(3):
+        for p in range(u):
+            i = (1 - j) * u + p + pad
+            if 0 <= i < k:
+                packed[p, :, j, :] = src[:, :, i].t()
+    return packed.reshape(u * cout, 3, cin).to(dtype).contiguous()
+
+
+def conv1d_lrelu_fwd(x, w, bias, dilation=1, slope=1.0, alpha=1.0, add1=None, add2=None, out=None):
+    """y = ((conv1d_same(leaky_relu(x, slope), w, dilation) + bias (+ add1) (+ add2)) * alpha) in ONE launch, rounded once.
+    x [B, T, C] 16-bit channels-last, w [Ko, ksize, C] (pack_conv1d_weight / pack_upsample_weight), bias fp32 [Ko], add1 / add2
+    [B, T, Ko] -> y [B, T, Ko].  slope = 1: no activation.  `out` may be add1 or add2 itself, never x.  Anything outside the
+    kernel's envelope (include/dle_mi355x.h) raises ValueError."""
+    C.require_cuda(x, w, bias, add1, add2, out)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("conv1d_lrelu_fwd: 16-bit activations and weights only (got %s)" % x.dtype)
+    if x.dim() != 3 or w.dim() != 3 or not x.is_contiguous() or not w.is_contiguous() or w.dtype != x.dtype or w.shape[2] != x.shape[2]:
+        raise ValueError("conv1d_lrelu_fwd: x must be contiguous [B,T,C] and w contiguous [Ko,ksize,C] of x's dtype")
+    b, t, c = x.shape
+    ko, ks, _ = w.shape
+    if bias.dtype != torch.float32 or bias.numel() != ko or not bias.is_contiguous():
+        raise ValueError("conv1d_lrelu_fwd: bias must be contiguous fp32 [Ko]")
+    for a in (add1, add2):
+        if a is not None and (tuple(a.shape) != (b, t, ko) or a.dtype != x.dtype or not a.is_contiguous()):
+            raise ValueError("conv1d_lrelu_fwd: an addend must be a contiguous [B,T,Ko] tensor of x's dtype")
+    if out is None:
+        out = torch.empty((b, t, ko), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (b, t, ko) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("conv1d_lrelu_fwd: out must be a contiguous [B,T,Ko] tensor of x's dtype")
+    n_add = (add1 is not None) + (add2 is not None)
+    C.annotate(flops=2.0 * b * t * ko * ks * c, tag="conv1d %dx%dx%d k%d ks%d d%d +%d" % (b, t, c, ko, ks, dilation, n_add),
+               bytes=float(x.numel() + w.numel() + out.numel() * (1 + n_add)) * 2)
+    C.call("dle_conv1d_lrelu_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(add1), C.ptr(add2), C.ptr(out), b, t, c, ko, ks,
+           int(dilation), float(slope), float(alpha), C.dt(x), C.stream())
+    return out
+
+
+def hfg_post_fwd(x, w, bias, slope=0.01, out=None):
+    """audio [B, T] fp32 = tanh(conv1d_same(leaky_relu(x, slope), w) + bias): the one-channel output convolution of the HiFi-GAN
+    generator.  x [B, T, C] 16-bit (C % 8 == 0, C <= 64), w [ksize, C] of x's dtype, bias fp32 [1]."""
+    C.require_cuda(x, w, bias, out)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("hfg_post_fwd: 16-bit activations and weights only (got %s)" % x.dtype)
+    if x.dim() != 3 or w.dim() != 2 or not x.is_contiguous() or not w.is_contiguous() or w.dtype != x.dtype or w.shape[1] != x.shape[2]:
+        raise ValueError("hfg_post_fwd: x must be contiguous [B,T,C] and w contiguous [ksize,C] of x's dtype")
+    if bias.dtype != torch.float32 or bias.numel() != 1:
+        raise ValueError("hfg_post_fwd: bias must be fp32 [1]")
+    b, t, c = x.shape
+    if out is None:
+        out = torch.empty((b, t), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (b, t) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("hfg_post_fwd: out must be a contiguous fp32 [B,T] tensor")
+    C.annotate(flops=2.0 * b * t * w.numel(), tag="hfg_post %dx%dx%d ks%d" % (b, t, c, w.shape[0]),
+               bytes=float(x.numel()) * 2 + out.numel() * 4)
+    C.call("dle_hfg_post_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(out), b, t, c, w.shape[0], float(slope), C.dt(x), C.stream())
+    return out

@@ -853,6 +853,23 @@ int dle_gemm_colsum_bits(const void* A, const void* B, void* C, const void* bits
                          int64_t ldb, int dtype, int accumulate_colsum, void* workspace, int64_t workspace_bytes,
                          hipStream_t stream);
 
+/* ---- HiFi-GAN generator, inference (csrc/hifigan.hip; SpeechSynthesis/HiFiGAN/hifigan/models.py) ----------------------------
+ * Activations channels-last [B, T, C], 16-bit; weights 16-bit; fp32 accumulation on MFMA; no allocation, no synchronisation.
+ * dle_conv1d_lrelu_fwd: "same" dilated Conv1d with the leaky ReLU that precedes it and the elementwise steps that follow it:
+ *     a[b,t,c]  = x < 0 ? round16(fl32(float(x) * slope)) : x                  (slope == 1: a = x; applied once, where the tile is staged)
+ *     acc       = sum_k sum_c float(w[ko,k,c]) * float(a[b, t + (k - (ksize-1)/2) * dilation, c])       (0 outside [0, T))
+ *     y[b,t,ko] = round16((acc + bias[ko] (+ add1[b,t,ko]) (+ add2[b,t,ko])) * alpha)                   (one rounding)
+ *   w [Ko, ksize, C] = torch's Conv1d weight permuted (0, 2, 1); bias fp32 [Ko]; add1 / add2 16-bit [B, T, Ko] or NULL.
+ *   Envelope: C, Ko multiples of 8 in [8, 2048]; ksize odd in [1, 11]; dilation >= 1 with (ksize-1)/2 * dilation <= 36; B >= 0,
+ *   T >= 1; every tensor < 4 GiB; operands 16-byte aligned.  y must not overlap x.  y MAY be add1 or add2 itself (the same base
+ *   pointer: every element is read by the lane that then writes it); a partial overlap is an error.
+ * dle_hfg_post_fwd: audio[b,t] = tanhf(bias[0] + sum_k sum_c float(w[k,c]) * float(a[b, t + k - (ksize-1)/2, c])), fp32 [B, T],
+ *   `a` as above; w 16-bit [ksize, C]; C a multiple of 8 in [8, 64], ksize odd in [1, 11]. */
+int dle_conv1d_lrelu_fwd(const void* x, const void* w, const float* bias, const void* add1, const void* add2, void* y, int B, int T,
+                         int C, int Ko, int ksize, int dilation, float slope, float alpha, int dtype, hipStream_t stream);
+int dle_hfg_post_fwd(const void* x, const void* w, const float* bias, float* audio, int B, int T, int C, int ksize, float slope,
+                     int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
