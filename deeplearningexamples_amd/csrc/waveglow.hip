@@ -668,8 +668,8 @@ extern "C" int dle_wg_taps_bwd(const void* dcol, const void* addend, void* dx, i
                                int dilation, int left, int64_t ld_add, int64_t ld_dx, int dtype, hipStream_t stream) {
   DLE_CHECK_ARG(dcol && dx && B > 0 && T > 0 && C > 0 && ntaps > 0, "wg_taps_bwd: bad args");
   WG_DT_CHECK("wg_taps_bwd");
-  DLE_CHECK_ARG(C % 8 == 0 && ld_dx % 8 == 0 && (!addend || ld_add % 8 == 0) && WG_AL16(dcol) && WG_AL16(dx) &&
-                WG_AL16(addend), "wg_taps_bwd: C, ld %% 8 == 0 and 16-byte aligned tensors");
+  DLE_CHECK_ARG(C % 8 == 0 && ld_dx % 8 == 0 && ld_dx >= C && (!addend || (ld_add % 8 == 0 && ld_add >= C)) && WG_AL16(dcol) &&
+                WG_AL16(dx) && WG_AL16(addend), "wg_taps_bwd: C, ld %% 8 == 0, ld >= C and 16-byte aligned tensors");
   const long long total = (long long)B * T * (C / 8);
   if (dtype == DLE_F16)
     hipLaunchKernelGGL(wg_taps_bwd_kernel<DLE_F16>, dim3(wg_grid(total)), dim3(WG_BLOCK), 0, stream, (const uint4_t*)dcol,
