@@ -330,6 +330,8 @@ extern "C" int dle_t2_lstm_gemm_fwd(const void* x, int64_t ldx, const void* w, i
                 al16(gates) && al16(c_prev) && al16(c_out) && (!bias || al16(bias)) && (!addend || (((uintptr_t)addend) & 7) == 0) &&
                 (!d0 || (al16(d0) && (ld0 & 7) == 0)) && (!d1 || (al16(d1) && (ld1 & 7) == 0)) && (!d2 || (al16(d2) && (ld2 & 7) == 0)),
                 "t2_lstm_gemm_fwd: H, K and every row pitch must be multiples of 8 with 16-byte aligned bases");
+  DLE_CHECK_ARG(ldx >= K && ldw >= K && ld_g >= 4LL * H && (!d0 || ld0 >= H) && (!d1 || ld1 >= H) && (!d2 || ld2 >= H),
+                "t2_lstm_gemm_fwd: a row pitch is smaller than its row (K, 4 H or H)");
   DLE_CHECK_ARG((long long)B * ldx * 2 < 0xFFFFFFE0LL && (long long)4 * H * ldw * 2 < 0xFFFFFFE0LL, "t2_lstm_gemm_fwd: operand above 4 GiB");
   SmallMArgs p = {(const unsigned short*)x, (const unsigned short*)w, gates, bias, (const unsigned short*)addend, B, 4 * H, K,
                   (long long)ldx, (long long)ldw, (long long)ld_g, dtype, addend ? 1 : 0, 0, 1.0f};

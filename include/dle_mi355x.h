@@ -783,7 +783,8 @@ int dle_t2_lstm_fwd(void* gates, int64_t ld_g, const float* c_prev, float* c_out
 /* One LSTMCell of the decoder in ONE launch (the few-row weight-streaming kernel of csrc/gemm_smallm.hip with the cell as its
  * epilogue): gates [B, 4H] = x [B, K] w [4H, K]^T (+ bias[4H]) (+ addend [B, 4H], 16-bit, row pitch ld_g), rounded to 16 bits as
  * the unfused dle_gemm output would be, then exactly dle_t2_lstm_fwd: activations to `gates`, c_out, dropout(h) to d0..d2.
- * H, K and every pitch multiples of 8, 16-byte aligned bases. */
+ * H, K and every pitch multiples of 8 and no pitch below its row (K, 4H, H), 16-byte aligned bases; keep_index is any bit
+ * position, as for dle_t2_lstm_fwd. */
 int dle_t2_lstm_gemm_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, const void* addend,
                          const float* c_prev, float* c_out, void* gates, int64_t ld_g, void* d0, int64_t ld0, void* d1, int64_t ld1,
                          void* d2, int64_t ld2, const void* keep, int64_t keep_index, float inv_keep, int B, int H, int K, int dtype,

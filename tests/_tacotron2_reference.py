@@ -1,5 +1,6 @@
 """float64 statements, derived per-element bars, input builders, case tables and a faulty float32 model for the twelve training
-kernels of csrc/tacotron2.hip (everything above its inference section): t2_tanh, t2_lstm_{fwd,bwd}<DT, VEC = true | false>,
+kernels of csrc/tacotron2.hip (the decoder-step launches -- its inference section and the cell fused into the gates product,
+dle_t2_lstm_gemm_fwd -- have theirs in tests/_tacotron2_step_reference.py, on this module's helpers): t2_tanh, t2_lstm_{fwd,bwd}<DT, VEC = true | false>,
 t2_attention_{fwd,bwd} without and with the fused location term (wloc / wlocT), t2_location_bwd, t2_mel_loss (+ t2_sum), t2_mask_rows,
 t2_sum_steps.  tests/ only: no GPU and no ctypes in here.  The helpers (U, ulp, stored, ratio, worst, bits, same_cast, gen, C_EXP,
 C_RCP) are those of tests/_smallops_reference.py.

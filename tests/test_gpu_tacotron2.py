@@ -76,9 +76,10 @@ def test_lstm_cell_forward_backward(cuda, dtype, b, h, with_drop, with_live):
 @pytest.mark.parametrize("b,h,k,bias,add,drop", [(128, 1024, 1536, False, True, True), (128, 1024, 2560, True, False, True),
                                                  (3, 96, 160, True, True, False), (70, 32, 72, False, False, True), (200, 64, 64, True, True, True)])
 def test_lstm_cell_fused_into_the_gates_product(cuda, dtype, b, h, k, bias, add, drop):
-    """dle_t2_lstm_gemm_fwd (the cell as the epilogue of the few-row GEMM) == dle_gemm followed by dle_t2_lstm_fwd BIT FOR BIT (the
-    pre-activation is rounded to the storage type exactly as the unfused product's output is), on strided operand / destination
-    views as the decoder uses them; both against the double."""
+    """dle_t2_lstm_gemm_fwd (the cell as the epilogue of the few-row GEMM) against dle_gemm followed by dle_t2_lstm_fwd: the gate
+    activations BIT FOR BIT (the pre-activation is rounded to the storage type exactly as the unfused product's output is), c_out
+    and the hidden states within 2^-9 max(1, max|r|), on strided operand / destination views as the decoder uses them; both against
+    the double.  The per-element statement of the fused launch is tests/test_gpu_tacotron2_step_reference.py."""
     ops = _ops()
     from deeplearningexamples_amd import functional as F, _cabi as C
     g = torch.Generator().manual_seed(b + h + k)
