@@ -237,6 +237,13 @@ _SIGS = {
                                    c_void_p, c_void_p, c_i64, c_u64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dle_conv1d_lrelu_fwd": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float, c_float, c_int, c_void_p]),
     "dle_hfg_post_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float, c_int, c_void_p]),
+    "dle_conv1d_packed_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_i64, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "dle_fp_relu_layernorm_fwd": (c_int, [c_void_p] * 7 + [c_i64, c_int, c_int, c_float, c_int, c_void_p]),
+    "dle_fp_embed": (c_int, [c_void_p] * 6 + [c_int, c_int, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
+    "dle_fp_scalar_conv_add": (c_int, [c_void_p] * 5 + [c_int, c_int, c_i64, c_int, c_int, c_int, c_void_p]),
+    "dle_fp_durations": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_i64, c_float, c_float, c_int, c_void_p]),
+    "dle_fp_expand": (c_int, [c_void_p] * 7 + [c_int, c_int, c_i64, c_int, c_i64, c_int, c_int, c_int, c_void_p]),
+    "dle_fp_unpack_mel": (c_int, [c_void_p] * 4 + [c_int, c_i64, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -1757,3 +1757,182 @@ def hfg_post_fwd(x, w, bias, slope=0.01, out=None):
                bytes=float(x.numel()) * 2 + out.numel() * 4)
     C.call("dle_hfg_post_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(out), b, t, c, w.shape[0], float(slope), C.dt(x), C.stream())
     return out
+
+
+# ------------------------------------------------------------------ FastPitch on packed utterances (csrc/fastpitch.hip)
+_FP16 = (torch.float16, torch.bfloat16)
+
+
+def _fp_table(name, cu, what="cu_seqlens"):
+    if cu is None or cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous int32 tensor [B + 1]" % (name, what))
+    return cu.numel() - 1
+
+
+def _fp_f32(name, t, shape, what):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous fp32 %s" % (name, what, list(shape)))
+
+
+def _fp_out(name, out, shape, dtype, device, what="out"):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor %s" % (name, what, dtype, list(shape)))
+    return out
+
+
+def conv1d_packed_fwd(x, w, bias, cu_seqlens, max_len, slope=1.0, add1=None, out=None):
+    """y = conv1d_same(act(x), w) + bias (+ add1) per SEQUENCE of a packed x [total, C] (16-bit, channels-last; sequence b owns rows
+    cu_seqlens[b] .. cu_seqlens[b + 1] - 1; rows outside a row's own sequence read as zero), one launch, one rounding.  w [Ko, ksize, C]
+    (pack_conv1d_weight), bias fp32 [Ko], add1 [total, Ko] or None.  slope 1: no activation; slope 0: ReLU on the input.  `out` may
+    be add1 itself, never x.  Anything outside the kernel's envelope (include/dle_mi355x.h) raises ValueError."""
+    C.require_cuda(x, w, bias, cu_seqlens, add1, out)
+    name = "conv1d_packed_fwd"
+    if x.dtype not in _FP16:
+        raise ValueError("%s: 16-bit activations and weights only (got %s)" % (name, x.dtype))
+    if x.dim() != 2 or w.dim() != 3 or not x.is_contiguous() or not w.is_contiguous() or w.dtype != x.dtype or w.shape[2] != x.shape[1]:
+        raise ValueError("%s: x must be contiguous [total,C] and w contiguous [Ko,ksize,C] of x's dtype" % name)
+    total, c = x.shape
+    ko, ks, _ = w.shape
+    b = _fp_table(name, cu_seqlens)
+    _fp_f32(name, bias, (ko,), "bias")
+    if add1 is not None and (tuple(add1.shape) != (total, ko) or add1.dtype != x.dtype or not add1.is_contiguous()):
+        raise ValueError("%s: add1 must be a contiguous [total,Ko] tensor of x's dtype" % name)
+    out = _fp_out(name, out, (total, ko), x.dtype, x.device)
+    C.annotate(flops=2.0 * total * ko * ks * c, tag="conv1d_packed %dx%d k%d ks%d B%d" % (total, c, ko, ks, b),
+               bytes=float(x.numel() + w.numel() + out.numel() * (2 if add1 is not None else 1)) * 2)
+    C.call("dle_conv1d_packed_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(add1), C.ptr(out), C.ptr(cu_seqlens), b, int(max_len),
+           total, c, ko, ks, float(slope), C.dt(x), C.stream())
+    return out
+
+
+def fp_relu_layernorm_fwd(x, gamma, beta, eps=1e-5, fc_w=None, fc_b=None, want_y=True, out=None, pred_out=None):
+    """y = LayerNorm(relu(x)) * gamma + beta on rows of x [rows, H] (16-bit), and -- with fc_w fp32 [n_pred, H], fc_b fp32 [n_pred] --
+    pred = y_rounded @ fc_w^T + fc_b as fp32 [rows, n_pred].  -> (y or None when want_y is False, pred or None)."""
+    C.require_cuda(x, gamma, beta, fc_w, fc_b, out, pred_out)
+    name = "fp_relu_layernorm_fwd"
+    if x.dtype not in _FP16 or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("%s: x must be a contiguous 16-bit [rows, H] tensor" % name)
+    rows, h = x.shape
+    _fp_f32(name, gamma, (h,), "gamma")
+    _fp_f32(name, beta, (h,), "beta")
+    n_pred = 0
+    if (fc_w is None) != (fc_b is None):
+        raise ValueError("%s: fc_w and fc_b come together" % name)
+    if fc_w is not None:
+        if fc_w.dim() != 2:
+            raise ValueError("%s: fc_w must be fp32 [n_pred, H]" % name)
+        n_pred = fc_w.shape[0]
+        _fp_f32(name, fc_w, (n_pred, h), "fc_w")
+        _fp_f32(name, fc_b, (n_pred,), "fc_b")
+    if not want_y and not n_pred:
+        raise ValueError("%s: neither y nor pred is wanted" % name)
+    y = _fp_out(name, out, (rows, h), x.dtype, x.device) if want_y else None
+    pred = _fp_out(name, pred_out, (rows, n_pred), torch.float32, x.device, "pred_out") if n_pred else None
+    C.annotate(bytes=float(x.numel()) * 2 * (2 if want_y else 1), tag="relu_ln R%dxH%d p%d" % (rows, h, n_pred))
+    C.call("dle_fp_relu_layernorm_fwd", C.ptr(x), C.ptr(y), C.ptr(gamma), C.ptr(beta), C.ptr(fc_w), C.ptr(fc_b), C.ptr(pred), rows, h,
+           n_pred, float(eps), C.dt(x), C.stream())
+    return y, pred
+
+
+def fp_embed(ids, word, pos, cu_seqlens, max_len, dtype, spk=None, out=None):
+    """y[r] = round16(word[ids[r]] + pos[position of r in its sequence] (+ spk)): ids int64 [total] packed, word fp32 [n_symbols, D],
+    pos fp32 [n_pos >= max_len, D], spk fp32 [D] or None -> [total, D] of `dtype`."""
+    C.require_cuda(ids, word, pos, cu_seqlens, spk, out)
+    name = "fp_embed"
+    if dtype not in _FP16:
+        raise ValueError("%s: 16-bit output only (got %s)" % (name, dtype))
+    if ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("%s: ids must be a contiguous int64 tensor [total]" % name)
+    if word.dim() != 2 or pos.dim() != 2:
+        raise ValueError("%s: word and pos must be fp32 [rows, D]" % name)
+    d = word.shape[1]
+    _fp_f32(name, word, (word.shape[0], d), "word")
+    _fp_f32(name, pos, (pos.shape[0], d), "pos")
+    if spk is not None:
+        _fp_f32(name, spk, (d,), "spk")
+    b = _fp_table(name, cu_seqlens)
+    total = ids.numel()
+    out = _fp_out(name, out, (total, d), dtype, ids.device)
+    C.call("dle_fp_embed", C.ptr(ids), C.ptr(word), C.ptr(pos), C.ptr(spk), C.ptr(out), C.ptr(cu_seqlens), b, int(max_len), total,
+           word.shape[0], pos.shape[0], d, C.dt(dtype), C.stream())
+    return out
+
+
+def fp_scalar_conv_add_(enc, v, w, bias, cu_seqlens, max_len):
+    """enc[r, c] += bias[c] + sum_k w[c, k] v[r + k - (ksize - 1) / 2] in place (v zero outside the sequence): the Conv1d(1 -> D, k) of
+    pitch_emb / energy_emb.  enc [total, D] 16-bit, v fp32 [total], w fp32 [D, ksize], bias fp32 [D]."""
+    C.require_cuda(enc, v, w, bias, cu_seqlens)
+    name = "fp_scalar_conv_add"
+    if enc.dtype not in _FP16 or enc.dim() != 2 or not enc.is_contiguous():
+        raise ValueError("%s: enc must be a contiguous 16-bit [total, D] tensor" % name)
+    total, d = enc.shape
+    _fp_f32(name, v, (total,), "v")
+    if w.dim() != 2:
+        raise ValueError("%s: w must be fp32 [D, ksize]" % name)
+    _fp_f32(name, w, (d, w.shape[1]), "w")
+    _fp_f32(name, bias, (d,), "bias")
+    b = _fp_table(name, cu_seqlens)
+    C.annotate(bytes=float(enc.numel()) * 4, tag="scalar_conv R%dxD%d" % (total, d), replay=False)       # (adds into enc)
+    C.call("dle_fp_scalar_conv_add", C.ptr(enc), C.ptr(v), C.ptr(w), C.ptr(bias), C.ptr(cu_seqlens), b, int(max_len), total, d,
+           w.shape[1], C.dt(enc), C.stream())
+    return enc
+
+
+def fp_durations(src, cu_seqlens, max_len, pace=1.0, max_duration=75.0, from_log=True, max_out=1024):
+    """Durations -> repetitions and the output sequence table (one workgroup).  src fp32 [total]: log durations (from_log: dur =
+    clamp(exp(src) - 1, 0, max_duration)) or durations.  reps = (int)(dur / pace + 0.5f).
+    -> (dur_pred fp32 [total] or None, reps int32 [total], tok_start int32 [total], cu_out int32 [B + 1])."""
+    C.require_cuda(src, cu_seqlens)
+    name = "fp_durations"
+    if src.dim() != 1:
+        raise ValueError("%s: src must be fp32 [total]" % name)
+    total = src.numel()
+    _fp_f32(name, src, (total,), "src")
+    b = _fp_table(name, cu_seqlens)
+    if not (float(pace) > 0.0):
+        raise ValueError("%s: pace must be positive (got %r)" % (name, pace))
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=src.device)
+    dur = torch.empty(total, dtype=torch.float32, device=src.device) if from_log else None
+    reps, tok_start, cu_out = i32(total), i32(total), i32(b + 1)
+    C.call("dle_fp_durations", C.ptr(src), int(bool(from_log)), C.ptr(dur), C.ptr(reps), C.ptr(tok_start), C.ptr(cu_out),
+           C.ptr(cu_seqlens), b, int(max_len), total, float(pace), float(max_duration), int(max_out), C.stream())
+    return dur, reps, tok_start, cu_out
+
+
+def fp_expand(enc, pos, reps, tok_start, cu_in, cu_out, max_in, max_out, total_out, out=None):
+    """The length regulator as a gather + the decoder's positional embedding: y[cu_out[b] + p] = round16(enc[j] + pos[p]), j the token
+    of sequence b that covers frame p.  enc [total_in, D] 16-bit, pos fp32 [n_pos >= max_out, D] -> [total_out, D]."""
+    C.require_cuda(enc, pos, reps, tok_start, cu_in, cu_out, out)
+    name = "fp_expand"
+    if enc.dtype not in _FP16 or enc.dim() != 2 or not enc.is_contiguous():
+        raise ValueError("%s: enc must be a contiguous 16-bit [total_in, D] tensor" % name)
+    total_in, d = enc.shape
+    if pos.dim() != 2:
+        raise ValueError("%s: pos must be fp32 [n_pos, D]" % name)
+    _fp_f32(name, pos, (pos.shape[0], d), "pos")
+    for t, what in ((reps, "reps"), (tok_start, "tok_start")):
+        if t.dtype != torch.int32 or tuple(t.shape) != (total_in,) or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous int32 tensor [total_in]" % (name, what))
+    b = _fp_table(name, cu_in, "cu_in")
+    if _fp_table(name, cu_out, "cu_out") != b:
+        raise ValueError("%s: cu_in and cu_out differ in length" % name)
+    out = _fp_out(name, out, (int(total_out), d), enc.dtype, enc.device)
+    C.call("dle_fp_expand", C.ptr(enc), C.ptr(pos), C.ptr(reps), C.ptr(tok_start), C.ptr(cu_in), C.ptr(cu_out), C.ptr(out), b,
+           int(max_in), total_in, int(max_out), int(total_out), pos.shape[0], d, C.dt(enc), C.stream())
+    return out
+
+
+def fp_unpack_mel(x, bias, cu_seqlens, t_pad, out=None):
+    """Packed [total, n_mel] 16-bit -> fp32 [B, n_mel, t_pad]; the frames behind a sequence's length hold bias (fp32 [n_mel])."""
+    C.require_cuda(x, bias, cu_seqlens, out)
+    name = "fp_unpack_mel"
+    if x.dtype not in _FP16 or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("%s: x must be a contiguous 16-bit [total, n_mel] tensor" % name)
+    total, n_mel = x.shape
+    _fp_f32(name, bias, (n_mel,), "bias")
+    b = _fp_table(name, cu_seqlens)
+    out = _fp_out(name, out, (b, n_mel, int(t_pad)), torch.float32, x.device)
+    C.call("dle_fp_unpack_mel", C.ptr(x), C.ptr(bias), C.ptr(out), C.ptr(cu_seqlens), b, total, n_mel, int(t_pad), C.dt(x), C.stream())
+    return out

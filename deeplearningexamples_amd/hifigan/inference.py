@@ -101,7 +101,7 @@ def load_fields(fpath):
 
 def _reject_unbuilt(args, fields):
     if args.fastpitch is not None:
-        raise SystemExit("--fastpitch: FastPitch is not built; text to speech here is python -m deeplearningexamples_amd.tacotron2.inference")
+        raise SystemExit("--fastpitch: this entry point reads saved spectrograms; text to speech with FastPitch is python -m deeplearningexamples_amd.fastpitch.inference")
     if args.waveglow is not None:
         raise SystemExit("--waveglow: the WaveGlow vocoder is python -m deeplearningexamples_amd.waveglow.inference")
     if args.torchscript:

@@ -871,6 +871,60 @@ int dle_conv1d_lrelu_fwd(const void* x, const void* w, const float* bias, const 
 int dle_hfg_post_fwd(const void* x, const void* w, const float* bias, float* audio, int B, int T, int C, int ksize, float slope,
                      int dtype, hipStream_t stream);
 
+/* ---- FastPitch, inference on PACKED utterances (csrc/fastpitch.hip; SpeechSynthesis/FastPitch/fastpitch/model.py:327-385) ----
+ * Activations 16-bit channels-last [total_rows, C]; sequence b owns rows cu[b] .. cu[b + 1] - 1 of a DEVICE int32 table
+ * cu[B + 1] (cu[0] = 0).  No padding rows, no masks: rows outside a row's OWN sequence read as zero, so every utterance gets what
+ * the reference gives it at batch 1.  Common envelope: B >= 1, 1 <= max_len <= 1024, total >= 1 (those of dle_attention_fwd_varlen).
+ * Lengths are clamped to [0, max_len] and rows to `total` inside every kernel: a wrong table gives wrong answers but reaches no
+ * memory outside the operands.  No allocation, no synchronisation, the caller's stream; 0 = ok, -1 / a HIP error otherwise
+ * (dle_last_error).
+ *
+ * dle_conv1d_packed_fwd: "same" Conv1d, dilation 1 (transformer.py:47-52 CoreNet's two convolutions with the ReLU between them,
+ *   common/layers.py:79-86 ConvReLUNorm's convolution), per sequence:
+ *     a[r,c]  = x < 0 ? round16(fl32(float(x) * slope)) : x        (slope 1: no activation; slope 0: ReLU; applied once, at staging)
+ *     acc     = sum_k sum_c float(w[ko,k,c]) * float(a[r + k - (ksize-1)/2, c])                (0 outside the row's own sequence)
+ *     y[r,ko] = round16(acc + bias[ko] (+ add1[r,ko]))                                          (fp32 accumulation on MFMA, one rounding)
+ *   w [Ko, ksize, C] = torch's Conv1d weight permuted (0, 2, 1); bias fp32 [Ko]; add1 16-bit [total, Ko] or NULL, and it may be y
+ *   itself (the same base pointer).  C, Ko multiples of 8 in [8, 2048]; ksize odd in [1, 11]; tensors < 4 GiB, 16-byte aligned;
+ *   y must not overlap x.  One workgroup per (sequence, 64-row tile, 128-channel block).
+ * dle_fp_relu_layernorm_fwd: the tail of ConvReLUNorm (common/layers.py:86-87) and TemporalPredictor.fc (model.py:103,108):
+ *     t = relu(x);  y[r,:] = round16((t - mean) * rstd * gamma + beta)   (fp32 statistics, biased variance, rstd = rsqrt(var + eps))
+ *     pred[r,j] = fc_b[j] + sum_c fc_w[j,c] * float(y[r,c])               (fp32 [rows, n_pred], on the ROUNDED y; n_pred = 0: none)
+ *   H a multiple of 8, <= 1024; n_pred in [0, 4]; fc_w fp32 [n_pred, H]; y may be NULL when only pred is wanted.
+ * dle_fp_embed: y[r,:] = round16((word[ids[r],:] + pos[p,:]) (+ spk[:])), p = r's position inside its sequence (transformer.py:200-207
+ *   with model.py:331-337); ids int64 [total] (clamped to the table), word fp32 [n_symbols, D], pos fp32 [n_pos >= max_len, D], spk
+ *   fp32 [D] or NULL; fp32 additions in that order.
+ * dle_fp_scalar_conv_add: pitch_emb / energy_emb (model.py:183-186, 358-373), Conv1d(1 -> D, ksize) of an fp32 per-token series
+ *   v [total], added in place:  s = b[c]; for k = 0 .. ksize-1: s = fl(s + fl(w[c,k] * v[r + k - (ksize-1)/2]))  (0 outside the
+ *   sequence);  enc[r,c] = round16(fl(float(enc[r,c]) + s)).  w fp32 [D, ksize], ksize odd in [1, 11].
+ * dle_fp_durations: model.py:344 and regulate_len's integer part (model.py:47-55), ONE workgroup.  from_log != 0: src = log
+ *   durations, dur = clamp(expf(src) - 1, 0, max_duration), written to dur_pred (fp32 [total], may be NULL); from_log == 0: src =
+ *   durations, dur_pred untouched.  reps[i] = (int)(dur / pace + 0.5f) in fp32 (IEEE division; negative or NaN: 0);
+ *   tok_start[i] = sum of reps of the tokens before i in its sequence; cu_out[B + 1] = prefix sum of the sequences' frame counts.
+ *   A sequence's frames are cut at max_out (its last tokens lose repetitions) so that tok_start and cu_out stay consistent.
+ *   All int32 (the reference casts the cumsum to fp16 under AMP, exact to 2048 only: not copied).  B <= 65536.
+ * dle_fp_expand: the length regulator (model.py:57-61) as a gather + the decoder's positional embedding (transformer.py:204-207):
+ *   y[cu_out[b] + p, :] = round16(float(enc[j,:]) + pos[p,:]), j = the token of sequence b with tok_start[j] <= p < tok_start[j] +
+ *   reps[j] (binary search per row; tokens with 0 repetitions vanish).  pos fp32 [n_pos >= max_out, D].
+ * dle_fp_unpack_mel: packed proj output [total_out, n_mel] 16-bit -> mel fp32 [B, n_mel, t_pad]; frames at and behind a sequence's
+ *   length hold bias[m] (what proj gives the reference's zeroed padding rows, model.py:381-384).  1 <= t_pad <= 1024. */
+int dle_conv1d_packed_fwd(const void* x, const void* w, const float* bias, const void* add1, void* y, const int32_t* cu_seqlens,
+                          int B, int max_len, int64_t total, int C, int Ko, int ksize, float slope, int dtype, hipStream_t stream);
+int dle_fp_relu_layernorm_fwd(const void* x, void* y, const float* gamma, const float* beta, const float* fc_w, const float* fc_b,
+                              float* pred, int64_t rows, int H, int n_pred, float eps, int dtype, hipStream_t stream);
+int dle_fp_embed(const int64_t* ids, const float* word, const float* pos, const float* spk, void* y, const int32_t* cu_seqlens,
+                 int B, int max_len, int64_t total, int n_symbols, int n_pos, int D, int dtype, hipStream_t stream);
+int dle_fp_scalar_conv_add(void* enc, const float* v, const float* w, const float* bias, const int32_t* cu_seqlens, int B, int max_len,
+                           int64_t total, int D, int ksize, int dtype, hipStream_t stream);
+int dle_fp_durations(const float* src, int from_log, float* dur_pred, int32_t* reps, int32_t* tok_start, int32_t* cu_out,
+                     const int32_t* cu_in, int B, int max_len, int64_t total, float pace, float max_duration, int max_out,
+                     hipStream_t stream);
+int dle_fp_expand(const void* enc, const float* pos, const int32_t* reps, const int32_t* tok_start, const int32_t* cu_in,
+                  const int32_t* cu_out, void* y, int B, int max_in, int64_t total_in, int max_out, int64_t total_out, int n_pos,
+                  int D, int dtype, hipStream_t stream);
+int dle_fp_unpack_mel(const void* x, const float* bias, float* mel, const int32_t* cu_seqlens, int B, int64_t total, int n_mel,
+                      int t_pad, int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
