@@ -244,6 +244,10 @@ _SIGS = {
     "dle_fp_durations": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_i64, c_float, c_float, c_int, c_void_p]),
     "dle_fp_expand": (c_int, [c_void_p] * 7 + [c_int, c_int, c_i64, c_int, c_i64, c_int, c_int, c_int, c_void_p]),
     "dle_fp_unpack_mel": (c_int, [c_void_p] * 4 + [c_int, c_i64, c_int, c_int, c_int, c_void_p]),
+    "dle_tcs_conv1d_packed_fwd": (c_int, [c_void_p] * 10 + [c_int, c_i64, c_i64] + [c_int] * 7 + [c_void_p]),
+    "dle_tcs_prefetch_mode": (c_int, [c_int]),
+    "dle_qn_normalize_pack": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_i64, c_int, c_void_p]),
+    "dle_ctc_greedy_packed": (c_int, [c_void_p] * 6 + [c_int, c_i64, c_int, c_int, c_void_p]),
 }
 
 _lib = None

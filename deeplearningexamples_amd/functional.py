@@ -1936,3 +1936,120 @@ def fp_unpack_mel(x, bias, cu_seqlens, t_pad, out=None):
     out = _fp_out(name, out, (b, n_mel, int(t_pad)), torch.float32, x.device)
     C.call("dle_fp_unpack_mel", C.ptr(x), C.ptr(bias), C.ptr(out), C.ptr(cu_seqlens), b, total, n_mel, int(t_pad), C.dt(x), C.stream())
     return out
+
+
+# ------------------------------------------------------------------ QuartzNet on packed utterances (csrc/quartznet.hip)
+def pack_depthwise_weight(w, dtype):
+    """torch's depthwise Conv1d weight [C, 1, ksize] (any device / float dtype) -> the [ksize, C] 16-bit tensor tcs_conv1d_packed_fwd
+    reads: a tap's channels are contiguous (one rounding per element)."""
+    if w.dim() != 3 or w.shape[1] != 1:
+        raise ValueError("pack_depthwise_weight: expected a [C, 1, ksize] weight (got %s)" % (tuple(w.shape),))
+    if dtype not in _FP16:
+        raise ValueError("pack_depthwise_weight: dtype must be torch.float16 or torch.bfloat16")
+    return w.detach()[:, 0, :].t().to(dtype).contiguous()
+
+
+def pad_ctc_decoder(weight, bias, dtype, rows=32):
+    """The decoder's Conv1d(k = 1) weight [n_classes, C] (or [n_classes, C, 1]) and bias [n_classes] -> (16-bit [rows, C], fp32
+    [rows]) with zero rows behind the classes: gemm then writes fp32 logits [total, rows] with 16-byte rows, and ctc_greedy_packed is
+    told n_classes and ld = rows, so the padding columns never count."""
+    if dtype not in _FP16:
+        raise ValueError("pad_ctc_decoder: dtype must be torch.float16 or torch.bfloat16")
+    w = weight.detach().reshape(weight.shape[0], -1)
+    n, c = w.shape
+    if bias.numel() != n or n > rows:
+        raise ValueError("pad_ctc_decoder: weight [%d, %d], bias %d, rows %d do not fit" % (n, c, bias.numel(), rows))
+    wp = torch.zeros((rows, c), dtype=dtype, device=w.device)
+    wp[:n] = w.to(dtype)
+    bp = torch.zeros((rows,), dtype=torch.float32, device=w.device)
+    bp[:n] = bias.detach().float()
+    return wp.contiguous(), bp.contiguous()
+
+
+def tcs_conv1d_packed_fwd(x, dw, pw, scale, shift, cu_in, cu_out=None, total_out=None, stride=1, dilation=1, residual=None,
+                          relu=True, out=None, d_out=None):
+    """One time-channel separable unit in one launch, per SEQUENCE of a packed x [total_in, C] (16-bit, channels-last):
+    d = round16(depthwise(x, dw)), y = round16(relu?(scale * (pw @ d) + shift (+ residual))).  dw [ksize, C] (pack_depthwise_weight),
+    pw [Ko, C], scale / shift fp32 [Ko], residual [total_out, Ko] or None, d_out [total_out, C] or None (receives d).  cu_in / cu_out
+    are device int32 [B + 1]; stride 1: cu_out defaults to cu_in and total_out to total_in; stride 2 needs both.  Anything outside the
+    kernel's envelope (include/dle_mi355x.h) raises ValueError."""
+    C.require_cuda(x, dw, pw, scale, shift, cu_in, cu_out, residual, out, d_out)
+    name = "tcs_conv1d_packed_fwd"
+    if x.dtype not in _FP16:
+        raise ValueError("%s: 16-bit activations and weights only (got %s)" % (name, x.dtype))
+    if x.dim() != 2 or dw.dim() != 2 or pw.dim() != 2 or not (x.is_contiguous() and dw.is_contiguous() and pw.is_contiguous()) or \
+            dw.dtype != x.dtype or pw.dtype != x.dtype or dw.shape[1] != x.shape[1] or pw.shape[1] != x.shape[1]:
+        raise ValueError("%s: x must be contiguous [total,C], dw contiguous [ksize,C] and pw contiguous [Ko,C] of x's dtype" % name)
+    total_in, c = x.shape
+    ks, ko = dw.shape[0], pw.shape[0]
+    b = _fp_table(name, cu_in, "cu_in")
+    if cu_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        cu_out = cu_in
+    elif _fp_table(name, cu_out, "cu_out") != b:
+        raise ValueError("%s: cu_in and cu_out must describe the same batch" % name)
+    if total_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        total_out = total_in
+    total_out = int(total_out)
+    _fp_f32(name, scale, (ko,), "scale")
+    _fp_f32(name, shift, (ko,), "shift")
+    if residual is not None and (tuple(residual.shape) != (total_out, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
+        raise ValueError("%s: residual must be a contiguous [total_out,Ko] tensor of x's dtype" % name)
+    out = _fp_out(name, out, (total_out, ko), x.dtype, x.device)
+    if d_out is not None:
+        d_out = _fp_out(name, d_out, (total_out, c), x.dtype, x.device, "d_out")
+    C.annotate(flops=2.0 * total_out * c * (ko + ks), tag="tcs %dx%d k%d ks%d s%d d%d B%d" % (total_in, c, ko, ks, stride, dilation, b),
+               bytes=float(x.numel() + dw.numel() + pw.numel() + out.numel() * (2 if residual is not None else 1)) * 2)
+    C.call("dle_tcs_conv1d_packed_fwd", C.ptr(x), C.ptr(dw), C.ptr(pw), C.ptr(scale), C.ptr(shift), C.ptr(residual), C.ptr(out),
+           C.ptr(d_out), C.ptr(cu_in), C.ptr(cu_out), b, total_in, total_out, c, ko, ks, int(stride), int(dilation), int(bool(relu)),
+           C.dt(x), C.stream())
+    return out
+
+
+def tcs_prefetch_mode(mode=-1):
+    """Which form of the fused separable kernel's chunk loop runs: 0 without the register prefetch of the next chunk, 1 with it, 2 by
+    grid size (the default); -1 only asks.  Returns the previous setting.  Both forms give the same bits (tests, A/B timing)."""
+    return int(C.lib().dle_tcs_prefetch_mode(int(mode)))
+
+
+def qn_normalize_pack(x, cu_seqlens, total, dtype, out=None):
+    """Per-feature normalisation over each utterance's own frames (unbiased std + 1e-5), the mask, the transpose and the 16-bit cast
+    in one launch: x fp32 [B, F, T_pad] -> packed [total, F] of `dtype`."""
+    C.require_cuda(x, cu_seqlens, out)
+    name = "qn_normalize_pack"
+    if dtype not in _FP16:
+        raise ValueError("%s: 16-bit output only (got %s)" % (name, dtype))
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("%s: x must be a contiguous fp32 [B, F, T_pad] tensor" % name)
+    b, f, t_pad = x.shape
+    if _fp_table(name, cu_seqlens) != b:
+        raise ValueError("%s: cu_seqlens must have B + 1 = %d entries" % (name, b + 1))
+    out = _fp_out(name, out, (int(total), f), dtype, x.device)
+    C.annotate(bytes=float(x.numel()) * 4 + float(out.numel()) * 2, tag="qn_normalize %dx%dx%d" % (b, f, t_pad))
+    C.call("dle_qn_normalize_pack", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(total), C.dt(dtype), C.stream())
+    return out
+
+
+def ctc_greedy_packed(logits, cu_seqlens, n_classes, want_logp=True, logp_out=None, ids_out=None, tokens_out=None, n_tokens_out=None):
+    """log_softmax, the first-maximum argmax and the CTC collapse (drop repeats, then blanks; blank = n_classes - 1) of packed fp32
+    logits [total, ld >= n_classes] in one launch -> (logp fp32 [total, n_classes] or None, ids int32 [total], tokens int32 [total]
+    packed per sequence at cu_seqlens[b], n_tokens int32 [B])."""
+    C.require_cuda(logits, cu_seqlens, logp_out, ids_out, tokens_out, n_tokens_out)
+    name = "ctc_greedy_packed"
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("%s: logits must be a contiguous fp32 [total, ld] tensor" % name)
+    total, ld = logits.shape
+    b = _fp_table(name, cu_seqlens)
+    dev = logits.device
+    logp = _fp_out(name, logp_out, (total, int(n_classes)), torch.float32, dev, "logp") if (want_logp or logp_out is not None) else None
+    ids = _fp_out(name, ids_out, (total,), torch.int32, dev, "ids")
+    tokens = _fp_out(name, tokens_out, (total,), torch.int32, dev, "tokens")
+    n_tokens = _fp_out(name, n_tokens_out, (b,), torch.int32, dev, "n_tokens")
+    C.annotate(bytes=float(logits.numel()) * 4 + (float(logp.numel()) * 4 if logp is not None else 0.0) + float(total) * 8,
+               tag="ctc_greedy %dx%d B%d" % (total, n_classes, b))
+    C.call("dle_ctc_greedy_packed", C.ptr(logits), C.ptr(logp), C.ptr(ids), C.ptr(tokens), C.ptr(n_tokens), C.ptr(cu_seqlens), b, total,
+           int(n_classes), ld, C.stream())
+    return logp, ids, tokens, n_tokens

@@ -925,6 +925,50 @@ int dle_fp_expand(const void* enc, const float* pos, const int32_t* reps, const 
 int dle_fp_unpack_mel(const void* x, const float* bias, float* mel, const int32_t* cu_seqlens, int B, int64_t total, int n_mel,
                       int t_pad, int dtype, hipStream_t stream);
 
+/* ---- QuartzNet, inference on PACKED utterances (csrc/quartznet.hip; SpeechRecognition/QuartzNet/quartznet/model.py:80-112,
+ * 207-292, 341-349; common/features.py:158-170, 290-302; common/helpers.py:35-61) ----------------------------------------------
+ * The conventions of the FastPitch block: activations 16-bit channels-last [total_rows, C]; sequence tables DEVICE int32 cu[B + 1],
+ * cu[0] = 0; starts and lengths are clamped inside every kernel (a wrong table gives wrong answers but reaches no memory outside the
+ * operands); no allocation, no synchronisation, the caller's stream; 0 = ok, -1 / a HIP error otherwise (dle_last_error); every
+ * operand 16-byte aligned, every tensor < 4 GiB; anything outside an envelope is an argument error, never a fallback.
+ *
+ * dle_tcs_conv1d_packed_fwd: ONE launch per time-channel separable unit (model.py:207-249, the `separable` branch: depthwise
+ *   MaskedConv1d -> pointwise MaskedConv1d -> BatchNorm1d(eps 1e-3), with JasperBlock.forward's residual sum and `mout` for the last
+ *   unit of a block).  For output row p of sequence b, len = cu_in[b+1] - cu_in[b], out_len = (len - 1) / stride + 1 =
+ *   cu_out[b+1] - cu_out[b] (stride 1: cu_out may be cu_in itself):
+ *     d[p,c]  = round16( sum_k float(dw[k,c]) * float(x[cu_in[b] + p*stride + (k - ksize/2)*dilation, c]) )     (index outside [0, len): 0)
+ *     y[p,ko] = round16( relu?( fmaf(scale[ko], sum_c float(pw[ko,c]) * float(d[p,c]), shift[ko]) + float(residual[p,ko]) ) )
+ *   Both sums accumulate in fp32: the depthwise as one fmaf chain over the taps in ascending order, the pointwise on MFMA over the
+ *   UNMODIFIED 16-bit weights (no folded copy).  d is rounded once to the storage type (what the reference's half-precision depthwise
+ *   convolution hands to its pointwise one) and never goes to HBM, except through d_out; y is rounded once.
+ *   dw [ksize, C] = torch's depthwise weight [C, 1, ksize] transposed; pw [Ko, C]; scale / shift fp32 [Ko]; residual 16-bit
+ *   [total_out, Ko] or NULL; d_out 16-bit [total_out, C] or NULL: the d tile as it is fed to the MFMA (y is bit-identical with and
+ *   without it).  Envelope: C, Ko multiples of 64 in [64, 1024]; ksize odd in [3, 127]; stride, dilation in {1, 2}, not both 2
+ *   (model.py:60-63); B >= 1; zero-length sequences produce nothing; no operand aliases another.
+ *   One workgroup per (sequence, tile of 64 OUTPUT rows, block of 256 output channels), C walked in chunks of 64 channels; the
+ *   depthwise thread owns a channel pair x 8 rows and takes the taps in blocks of 8.  Not persistent: no grid cap.  Two forms of
+ *   the chunk loop give the same bits: with a register prefetch of the next chunk (grids of at most one workgroup per CU) and
+ *   without.  dle_tcs_prefetch_mode(0 / 1 / 2): never / always / by grid size (the default); -1: query; returns the previous
+ *   setting (tests and A/B timing, as dle_gemm8_mode).
+ * dle_qn_normalize_pack: normalize_batch(.., "per_feature"), the mask, the transpose and the 16-bit cast (features.py:158-170,
+ *   290-302): x fp32 [B, F, T_pad] log-mel -> y[cu[b] + t, f] = round16((x[b,f,t] - mean_bf) / (std_bf + 1e-5)) for t < len_b; mean
+ *   and UNBIASED standard deviation over the sequence's own frames in fp32 (two passes); IEEE division.  F a multiple of 8, <= 128.
+ *   A sequence of one frame gives NaN as the reference does (the host rejects it).
+ * dle_ctc_greedy_packed: log_softmax + GreedyCTCDecoder + ctc_decoder_predictions_tensor (model.py:341-349, helpers.py:35-61).
+ *   logits fp32 [total, ld], the first n_classes <= ld columns of a row count; logp fp32 [total, n_classes] or NULL; ids int32 [total]
+ *   = the FIRST maximum of the row; tokens int32 [total]: packed per sequence at cu[b], the ids left after
+ *   `(p != previous or previous == blank) and p != blank` (previous = blank in front of the first row); n_tokens int32 [B];
+ *   blank = n_classes - 1.  One workgroup per sequence.  2 <= n_classes <= 4096. */
+int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const void* pw, const float* scale, const float* shift,
+                              const void* residual, void* y, void* d_out, const int32_t* cu_in, const int32_t* cu_out,
+                              int B, int64_t total_in, int64_t total_out, int C, int Ko, int ksize, int stride, int dilation,
+                              int relu, int dtype, hipStream_t stream);
+int dle_tcs_prefetch_mode(int mode);
+int dle_qn_normalize_pack(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int64_t total, int dtype,
+                          hipStream_t stream);
+int dle_ctc_greedy_packed(const float* logits, float* logp, int32_t* ids, int32_t* tokens, int32_t* n_tokens,
+                          const int32_t* cu_seqlens, int B, int64_t total, int n_classes, int ld, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
