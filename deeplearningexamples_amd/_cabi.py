@@ -248,6 +248,8 @@ _SIGS = {
     "dle_tcs_prefetch_mode": (c_int, [c_int]),
     "dle_qn_normalize_pack": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_i64, c_int, c_void_p]),
     "dle_ctc_greedy_packed": (c_int, [c_void_p] * 6 + [c_int, c_i64, c_int, c_int, c_void_p]),
+    "dle_conv1d_bn_packed_fwd": (c_int, [c_void_p] * 8 + [c_int, c_i64, c_i64] + [c_int] * 7 + [c_void_p]),
+    "dle_qn_normalize_pack_lead": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_i64, c_int, c_void_p]),
 }
 
 _lib = None

@@ -362,14 +362,22 @@ extern "C" int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const vo
 
 // ---- per-feature normalisation + mask + transpose + 16-bit cast ------------------------------------------------------------------
 // one workgroup per (sequence, 8 features): wavefront w takes the statistics of features 2w, 2w + 1 (two passes in fp32: the mean,
-// then the squared deviations from it), then every thread writes whole 16-byte groups of 8 features
+// then the squared deviations from it), then every thread writes whole 16-byte groups of 8 features.  `lead` zero rows stand in
+// front of every sequence (dle_qn_normalize_pack_lead; Jasper/inference.py:329-333): the table counts them, the statistics do not.
 template <int DT>
 __global__ __launch_bounds__(256) void qn_normalize_pack_kernel(const float* x, unsigned short* y, const int32_t* cu, long long total,
-                                                                int F, int t_pad) {
+                                                                int F, int t_pad, int lead) {
   __shared__ float s_mean[8], s_den[8];
   const int b = blockIdx.x, f0 = blockIdx.y * 8;
   long long start, len;
   qn_seq(cu, b, total, start, len);
+  if (lead > 0) {                                                   // workgroup-uniform
+    const long long nz = len < lead ? len : lead;
+    const ushort8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long long t = threadIdx.x; t < nz; t += 256) *(ushort8_t*)(y + (start + t) * F + f0) = zero;
+    start += nz;
+    len -= nz;
+  }
   if (len > t_pad) len = t_pad;
   if (len <= 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -399,8 +407,9 @@ __global__ __launch_bounds__(256) void qn_normalize_pack_kernel(const float* x, 
   }
 }
 
-extern "C" int dle_qn_normalize_pack(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int64_t total,
-                                     int dtype, hipStream_t stream) {
+extern "C" int dle_qn_normalize_pack_lead(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int lead,
+                                          int64_t total, int dtype, hipStream_t stream) {
+  DLE_CHECK_ARG(lead >= 0 && lead <= 65536, "qn_normalize_pack: lead must be in [0, 65536] (got %d)", lead);
   DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "qn_normalize_pack: 16-bit output only");
   DLE_CHECK_ARG(B >= 1 && B <= 65535 && total >= 0 && total < (1LL << 31), "qn_normalize_pack: bad batch / total rows");
   DLE_CHECK_ARG(F >= 8 && F <= 128 && F % 8 == 0, "qn_normalize_pack: F must be a multiple of 8, <= 128 (got %d)", F);
@@ -410,11 +419,16 @@ extern "C" int dle_qn_normalize_pack(const float* x, void* y, const int32_t* cu_
   DLE_CHECK_ARG(!(((uintptr_t)y) & 15) && !((((uintptr_t)x) | ((uintptr_t)cu_seqlens)) & 3), "qn_normalize_pack: y must be 16-byte aligned");
   const dim3 grid((unsigned)B, (unsigned)(F / 8)), block(256);
   if (dtype == DLE_F16)
-    hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_F16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad);
+    hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_F16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad, lead);
   else
-    hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_BF16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad);
+    hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_BF16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad, lead);
   DLE_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int dle_qn_normalize_pack(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int64_t total,
+                                     int dtype, hipStream_t stream) {
+  return dle_qn_normalize_pack_lead(x, y, cu_seqlens, B, F, T_pad, 0, total, dtype, stream);
 }
 
 // ---- log_softmax + argmax + the CTC collapse ---------------------------------------------------------------------------------------

@@ -2033,6 +2033,25 @@ def qn_normalize_pack(x, cu_seqlens, total, dtype, out=None):
     return out
 
 
+def qn_normalize_pack_lead(x, cu_seqlens, total, dtype, lead, out=None):
+    """qn_normalize_pack with `lead` zero rows in front of every utterance (Jasper's --pad_leading, applied to the normalised
+    features): cu_seqlens describes the OUTPUT rows, len_b + lead per sequence; the statistics run over the len_b real frames."""
+    C.require_cuda(x, cu_seqlens, out)
+    name = "qn_normalize_pack_lead"
+    if dtype not in _FP16:
+        raise ValueError("%s: 16-bit output only (got %s)" % (name, dtype))
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("%s: x must be a contiguous fp32 [B, F, T_pad] tensor" % name)
+    b, f, t_pad = x.shape
+    if _fp_table(name, cu_seqlens) != b:
+        raise ValueError("%s: cu_seqlens must have B + 1 = %d entries" % (name, b + 1))
+    out = _fp_out(name, out, (int(total), f), dtype, x.device)
+    C.annotate(bytes=float(x.numel()) * 4 + float(out.numel()) * 2, tag="qn_normalize %dx%dx%d lead %d" % (b, f, t_pad, lead))
+    C.call("dle_qn_normalize_pack_lead", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(lead), int(total), C.dt(dtype),
+           C.stream())
+    return out
+
+
 def ctc_greedy_packed(logits, cu_seqlens, n_classes, want_logp=True, logp_out=None, ids_out=None, tokens_out=None, n_tokens_out=None):
     """log_softmax, the first-maximum argmax and the CTC collapse (drop repeats, then blanks; blank = n_classes - 1) of packed fp32
     logits [total, ld >= n_classes] in one launch -> (logp fp32 [total, n_classes] or None, ids int32 [total], tokens int32 [total]
@@ -2053,3 +2072,44 @@ def ctc_greedy_packed(logits, cu_seqlens, n_classes, want_logp=True, logp_out=No
     C.call("dle_ctc_greedy_packed", C.ptr(logits), C.ptr(logp), C.ptr(ids), C.ptr(tokens), C.ptr(n_tokens), C.ptr(cu_seqlens), b, total,
            int(n_classes), ld, C.stream())
     return logp, ids, tokens, n_tokens
+
+
+# ------------------------------------------------------------------ Jasper on packed utterances (csrc/jasper.hip)
+def conv1d_bn_packed_fwd(x, w, scale, shift, cu_in, cu_out=None, total_out=None, stride=1, dilation=1, residual=None, relu=True,
+                         out=None):
+    """One Jasper sub-block in one launch, per SEQUENCE of a packed x [total_in, C] (16-bit, channels-last):
+    y = round16(relu?(scale * conv1d(x, w) + shift (+ residual))), 'same' padding, rows outside the sequence read as zero.
+    w [Ko, ksize, C] (pack_conv1d_weight, the layout of conv1d_lrelu_fwd), scale / shift fp32 [Ko], residual [total_out, Ko] or None.  cu_in / cu_out are device
+    int32 [B + 1]; stride 1: cu_out defaults to cu_in and total_out to total_in; stride 2 needs both.  Anything outside the
+    kernel's envelope (include/dle_mi355x.h) raises ValueError."""
+    C.require_cuda(x, w, scale, shift, cu_in, cu_out, residual, out)
+    name = "conv1d_bn_packed_fwd"
+    if x.dtype not in _FP16:
+        raise ValueError("%s: 16-bit activations and weights only (got %s)" % (name, x.dtype))
+    if x.dim() != 2 or w.dim() != 3 or not (x.is_contiguous() and w.is_contiguous()) or w.dtype != x.dtype or \
+            w.shape[2] != x.shape[1]:
+        raise ValueError("%s: x must be contiguous [total,C] and w contiguous [Ko,ksize,C] of x's dtype" % name)
+    total_in, c = x.shape
+    ko, ks = w.shape[0], w.shape[1]
+    b = _fp_table(name, cu_in, "cu_in")
+    if cu_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        cu_out = cu_in
+    elif _fp_table(name, cu_out, "cu_out") != b:
+        raise ValueError("%s: cu_in and cu_out must describe the same batch" % name)
+    if total_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        total_out = total_in
+    total_out = int(total_out)
+    _fp_f32(name, scale, (ko,), "scale")
+    _fp_f32(name, shift, (ko,), "shift")
+    if residual is not None and (tuple(residual.shape) != (total_out, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
+        raise ValueError("%s: residual must be a contiguous [total_out,Ko] tensor of x's dtype" % name)
+    out = _fp_out(name, out, (total_out, ko), x.dtype, x.device)
+    C.annotate(flops=2.0 * total_out * c * ko * ks, tag="conv1d_bn %dx%d k%d ks%d s%d d%d B%d" % (total_in, c, ko, ks, stride, dilation, b),
+               bytes=float(x.numel() + w.numel() + out.numel() * (2 if residual is not None else 1)) * 2)
+    C.call("dle_conv1d_bn_packed_fwd", C.ptr(x), C.ptr(w), C.ptr(scale), C.ptr(shift), C.ptr(residual), C.ptr(out), C.ptr(cu_in),
+           C.ptr(cu_out), b, total_in, total_out, c, ko, ks, int(stride), int(dilation), int(bool(relu)), C.dt(x), C.stream())
+    return out

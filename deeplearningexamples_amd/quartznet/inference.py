@@ -172,9 +172,10 @@ def latency_percentiles(seconds, ratios=(0.9, 0.95, 0.99), skip=5):
     return out
 
 
-def main(argv=None):
-    """-> dict(preds=[str], wer=float or None, logits=[host tensors])."""
-    args = parse_args(argv)
+def main(argv=None, parser=None, recognizer=None):
+    """-> dict(preds=[str], wer=float or None, logits=[host tensors]).  parser / recognizer: another recipe's command line over
+    the same modes (jasper/inference.py): its argparse parser and a function (ckpt, cfg, args, dtype, dev) -> recognizer."""
+    args = (parser or build_parser()).parse_args(argv)
     reject_unbuilt(args)
     cfg = apply_overrides(load_config(args.model_config), args.override_config)
     reject_unbuilt(args, cfg)
@@ -198,7 +199,10 @@ def main(argv=None):
     ckpt = torch.load(args.ckpt, map_location="cpu", weights_only=False)
     if args.ema and isinstance(ckpt, dict) and "state_dict" in ckpt and "ema_state_dict" not in ckpt:
         print("WARNING: EMA weights are unavailable in %s." % args.ckpt)
-    rec = QuartzNetRecognizer.from_checkpoint(ckpt, cfg, ema=args.ema, dtype=dtype, device=dev)
+    if recognizer is not None:
+        rec = recognizer(ckpt, cfg, args, dtype, dev)
+    else:
+        rec = QuartzNetRecognizer.from_checkpoint(ckpt, cfg, ema=args.ema, dtype=dtype, device=dev)
 
     if args.transcribe_wav:
         items, bs = [(args.transcribe_wav, None)], 1

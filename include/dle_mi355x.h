@@ -969,6 +969,31 @@ int dle_qn_normalize_pack(const float* x, void* y, const int32_t* cu_seqlens, in
 int dle_ctc_greedy_packed(const float* logits, float* logp, int32_t* ids, int32_t* tokens, int32_t* n_tokens,
                           const int32_t* cu_seqlens, int B, int64_t total, int n_classes, int ld, hipStream_t stream);
 
+/* ---- Jasper, inference on PACKED utterances (csrc/jasper.hip, csrc/quartznet.hip; SpeechRecognition/Jasper/jasper/model.py:58-85,
+ * 128-162; inference.py:329-333) ------------------------------------------------------------------------------------------------
+ * The conventions of the QuartzNet block above.
+ *
+ * dle_conv1d_bn_packed_fwd: ONE launch per Jasper sub-block: dense MaskedConv1d -> BatchNorm1d(eps 1e-3, evaluation mode), with
+ *   JasperBlock.forward's residual sum and activation for the last sub-block of a block.  For output row p of sequence b,
+ *   len = cu_in[b+1] - cu_in[b], out_len = (len - 1) / stride + 1 = cu_out[b+1] - cu_out[b] (stride 1: cu_out may be cu_in itself):
+ *     acc     = sum_k sum_c float(w[ko,k,c]) * float(x[cu_in[b] + p*stride + (k - ksize/2)*dilation, c])     (index outside [0, len): 0)
+ *     y[p,ko] = round16( relu?( fmaf(scale[ko], acc, shift[ko]) + float(residual[p,ko]) ) )
+ *   acc is fp32 on v_mfma_f32_32x32x16_{bf16,f16} over the UNMODIFIED 16-bit weights (no folded copy); y is rounded once.
+ *   w [Ko, ksize, C] = torch's Conv1d weight [Ko, C, ksize] permuted (0, 2, 1); scale / shift fp32 [Ko]; residual 16-bit
+ *   [total_out, Ko] or NULL.  Envelope: C, Ko multiples of 64 in [64, 1024]; ksize odd in [1, 29]; stride, dilation in {1, 2}, not
+ *   both 2 (model.py:52-55); B >= 1; no cap on the sequence length; zero-length sequences produce nothing; no operand aliases y.
+ *   One workgroup per (sequence, tile of 128 OUTPUT rows, block of 128 output channels), C walked in chunks of 64 channels; the
+ *   input rows of a chunk and the weight slab of a (chunk, tap) are staged in LDS once per workgroup, double-buffered (up to
+ *   118,368 bytes of dynamic LDS).  Not persistent: no grid cap.  The loop has one form.
+ * dle_qn_normalize_pack_lead: dle_qn_normalize_pack with `lead` >= 0 zero rows in front of every sequence (inference.py:329-333,
+ *   --pad_leading on the normalised features): cu describes the OUTPUT rows, len_b + lead per sequence; rows [0, lead) of a
+ *   sequence are zero, the statistics run over the len_b real frames; lead = 0 gives the bits of dle_qn_normalize_pack. */
+int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
+                             const int32_t* cu_in, const int32_t* cu_out, int B, int64_t total_in, int64_t total_out, int C, int Ko,
+                             int ksize, int stride, int dilation, int relu, int dtype, hipStream_t stream);
+int dle_qn_normalize_pack_lead(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int lead, int64_t total,
+                               int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
