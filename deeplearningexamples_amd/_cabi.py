@@ -250,6 +250,12 @@ _SIGS = {
     "dle_ctc_greedy_packed": (c_int, [c_void_p] * 6 + [c_int, c_i64, c_int, c_int, c_void_p]),
     "dle_conv1d_bn_packed_fwd": (c_int, [c_void_p] * 8 + [c_int, c_i64, c_i64] + [c_int] * 7 + [c_void_p]),
     "dle_qn_normalize_pack_lead": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_i64, c_int, c_void_p]),
+    "dle_txl_attention_supported": (c_int, [c_int, c_int, c_int]),
+    "dle_txl_attention_launch_count": (c_u64, []),
+    "dle_txl_rel_attention_fwd": (c_int, [c_void_p, c_i64] + [c_void_p] * 5 + [c_int] * 9 + [c_float, c_int, c_void_p]),
+    "dle_txl_kv_append": (c_int, [c_void_p, c_i64, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "dle_rows_gather_scale": (c_int, [c_void_p] * 4 + [c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_float, c_int, c_void_p]),
+    "dle_row_nll": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p]),
 }
 
 _lib = None

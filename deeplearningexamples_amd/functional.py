@@ -2113,3 +2113,120 @@ def conv1d_bn_packed_fwd(x, w, scale, shift, cu_in, cu_out=None, total_out=None,
     C.call("dle_conv1d_bn_packed_fwd", C.ptr(x), C.ptr(w), C.ptr(scale), C.ptr(shift), C.ptr(residual), C.ptr(out), C.ptr(cu_in),
            C.ptr(cu_out), b, total_in, total_out, c, ko, ks, int(stride), int(dilation), int(bool(relu)), C.dt(x), C.stream())
     return out
+
+
+# ------------------------------------------------------------------ Transformer-XL evaluation (csrc/transformer_xl.hip)
+def txl_attention_supported(qlen, klen, head_dim):
+    return bool(C.lib().dle_txl_attention_supported(int(qlen), int(klen), int(head_dim)))
+
+
+def txl_attention_launch_count():
+    """Launches of the relative attention kernel by this process so far."""
+    return int(C.lib().dle_txl_attention_launch_count())
+
+
+def _txl_i32(name, t, what, n=None):
+    if t is None:
+        return
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError("%s: %s must be a contiguous int32 vector%s" % (name, what, "" if n is None else " of %d" % n))
+
+
+def txl_rel_attention_fwd(q, u, v, kv, r, heads, qlen, mlen, start, shift, scale, out=None):
+    """Relative attention of one Transformer-XL layer and segment over the K / V ring: q [B*qlen, >= H] (a column slice of the
+    [.., 3H] projection is fine), u / v [heads, 64] (r_w_bias, r_r_bias), kv [B, cap, 2H] ring whose logical key j sits at row
+    (start + j) % cap, r [n_dist, H] by distance, allowed(i, j) = (i - shift < j) and (j <= i + mlen) -> ctx [B*qlen, H]."""
+    C.require_cuda(q, u, v, kv, r, out)
+    name = "txl_rel_attention_fwd"
+    heads, qlen, mlen, start, shift = int(heads), int(qlen), int(mlen), int(start), int(shift)
+    if q.dtype not in _FP16 or any(t.dtype != q.dtype for t in (u, v, kv, r)):
+        raise ValueError("%s: 16-bit operands of one dtype only" % name)
+    if kv.dim() != 3 or not kv.is_contiguous() or heads < 1 or kv.shape[2] != 2 * heads * 64:
+        raise ValueError("%s: kv must be a contiguous ring [B, cap, 2 * heads * 64]" % name)
+    b, cap, h = kv.shape[0], kv.shape[1], heads * 64
+    if tuple(u.shape) != (heads, 64) or tuple(v.shape) != (heads, 64) or not (u.is_contiguous() and v.is_contiguous()):
+        raise ValueError("%s: u and v must be contiguous [heads, 64]" % name)
+    if qlen < 1 or mlen < 0 or not txl_attention_supported(qlen, mlen + qlen, 64):
+        raise ValueError("%s: outside the kernel's envelope: qlen %d, mlen %d (1 <= qlen <= 512, klen <= 4096)" % (name, qlen, mlen))
+    klen = mlen + qlen
+    if not (klen <= cap <= 4096) or not (0 <= start < cap) or shift < 1:
+        raise ValueError("%s: needs klen <= cap <= 4096, 0 <= start < cap, shift >= 1 (got klen %d, cap %d, start %d, shift %d)"
+                         % (name, klen, cap, start, shift))
+    if q.dim() != 2 or q.shape[0] != b * qlen or q.shape[1] != h or q.stride(1) != 1 or q.stride(0) < h or q.stride(0) % 8:
+        raise ValueError("%s: q must be [B*qlen, H] with unit inner stride and a row pitch that is a multiple of 8" % name)
+    if r.dim() != 2 or r.shape[1] != h or r.shape[0] < klen or not r.is_contiguous():
+        raise ValueError("%s: r must be a contiguous [n_dist >= klen, H] table" % name)
+    out = _fp_out(name, out, (b * qlen, h), q.dtype, q.device)
+    C.annotate(flops=2.0 * b * heads * qlen * klen * 64 * 3, bytes=float(b) * (klen * 2 * h + 2 * qlen * h) * 2 + float(klen) * h * 2,
+               tag="txl_attn B%d h%d q%d m%d" % (b, heads, qlen, mlen))
+    C.call("dle_txl_rel_attention_fwd", C.ptr(q), q.stride(0), C.ptr(u), C.ptr(v), C.ptr(kv), C.ptr(r), C.ptr(out), b, heads, 64,
+           qlen, mlen, cap, start, r.shape[0], min(shift, 1 << 30), float(scale), C.dt(q), C.stream())
+    return out
+
+
+def txl_kv_append(qkv, kv, qlen, mlen, start):
+    """K and V thirds of the segment's projection qkv [B*qlen, 3H] -> rows (start + mlen + t) % cap of the ring kv [B, cap, 2H]."""
+    C.require_cuda(qkv, kv)
+    name = "txl_kv_append"
+    qlen, mlen, start = int(qlen), int(mlen), int(start)
+    if qkv.dtype not in _FP16 or kv.dtype != qkv.dtype:
+        raise ValueError("%s: 16-bit operands of one dtype only" % name)
+    if kv.dim() != 3 or not kv.is_contiguous() or kv.shape[2] % 16:
+        raise ValueError("%s: kv must be a contiguous ring [B, cap, 2H]" % name)
+    b, cap, h = kv.shape[0], kv.shape[1], kv.shape[2] // 2
+    if qkv.dim() != 2 or not qkv.is_contiguous() or tuple(qkv.shape) != (b * qlen, 3 * h):
+        raise ValueError("%s: qkv must be a contiguous [B*qlen, 3H] tensor" % name)
+    if qlen < 1 or mlen < 0 or mlen + qlen > cap or cap > 4096 or not (0 <= start < cap):
+        raise ValueError("%s: needs mlen + qlen <= cap <= 4096 and 0 <= start < cap (got %d, %d, %d, %d)" % (name, mlen, qlen, cap, start))
+    C.annotate(bytes=float(b) * qlen * 2 * h * 2 * 2, tag="txl_kv_append B%d q%d" % (b, qlen))
+    C.call("dle_txl_kv_append", C.ptr(qkv), qkv.stride(0), C.ptr(kv), b, h, qlen, mlen, cap, start, C.dt(qkv), C.stream())
+    return kv
+
+
+def rows_gather_scale(src, dst, rows, src_idx=None, dst_idx=None, scale=1.0):
+    """dst[dst_idx[r], :] = round16(scale * float(src[src_idx[r], :])) for r < rows; either int32 index list may be None (= r).
+    Rows whose index falls outside its tensor are skipped; destination rows must be distinct."""
+    C.require_cuda(src, dst, src_idx, dst_idx)
+    name = "rows_gather_scale"
+    rows = int(rows)
+    if src.dtype not in _FP16 or dst.dtype != src.dtype:
+        raise ValueError("%s: 16-bit operands of one dtype only" % name)
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1] or src.shape[1] % 8 or src.shape[1] == 0:
+        raise ValueError("%s: src and dst must be 2-D with one width, a multiple of 8" % name)
+    for t in (src, dst):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 8:
+            raise ValueError("%s: unit inner stride and a row pitch that is a multiple of 8" % name)
+    _txl_i32(name, src_idx, "src_idx", rows)
+    _txl_i32(name, dst_idx, "dst_idx", rows)
+    if rows < 0 or (src_idx is None and rows > src.shape[0]) or (dst_idx is None and rows > dst.shape[0]):
+        raise ValueError("%s: %d rows do not fit src %d / dst %d" % (name, rows, src.shape[0], dst.shape[0]))
+    if src.shape[0] == 0 or dst.shape[0] == 0:
+        raise ValueError("%s: empty source or destination" % name)
+    C.annotate(bytes=float(rows) * src.shape[1] * 4, tag="rows_gather_scale %dx%d" % (rows, src.shape[1]))
+    C.call("dle_rows_gather_scale", C.ptr(src), C.ptr(src_idx), C.ptr(dst), C.ptr(dst_idx), rows, src.shape[1], src.stride(0),
+           dst.stride(0), src.shape[0], dst.shape[0], float(scale), C.dt(src), C.stream())
+    return dst
+
+
+def row_nll(logits, target, nll, pos=None, n_classes=None, accumulate=False):
+    """nll[pos[r]] (+)= logsumexp(logits[r, :n_classes]) - logits[r, target[r]] on fp32 logits [rows, ld]; target / pos int32
+    [rows] (pos None = r; the positions of one call must be distinct); nll fp32 vector."""
+    C.require_cuda(logits, target, nll, pos)
+    name = "row_nll"
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError("%s: logits must be an fp32 [rows, ld] tensor with unit inner stride" % name)
+    rows = logits.shape[0]
+    n_classes = logits.shape[1] if n_classes is None else int(n_classes)
+    if not (1 <= n_classes <= 160003) or n_classes > logits.shape[1]:
+        raise ValueError("%s: 1 <= n_classes <= min(160003, ld) (got %d, ld %d)" % (name, n_classes, logits.shape[1]))
+    _txl_i32(name, target, "target", rows)
+    _txl_i32(name, pos, "pos", rows)
+    if target is None:
+        raise ValueError("%s: target is required" % name)
+    if nll.dtype != torch.float32 or nll.dim() != 1 or not nll.is_contiguous() or nll.numel() == 0 or \
+            (pos is None and rows > nll.numel()):
+        raise ValueError("%s: nll must be a contiguous fp32 vector with room for the rows" % name)
+    C.annotate(bytes=float(rows) * n_classes * 4, tag="row_nll %dx%d" % (rows, n_classes), replay=not accumulate)
+    C.call("dle_row_nll", C.ptr(logits), logits.stride(0), C.ptr(target), C.ptr(pos), C.ptr(nll), rows, n_classes, nll.numel(),
+           int(bool(accumulate)), C.stream())
+    return nll

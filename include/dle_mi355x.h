@@ -994,6 +994,48 @@ int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const float* scale, c
 int dle_qn_normalize_pack_lead(const float* x, void* y, const int32_t* cu_seqlens, int B, int F, int T_pad, int lead, int64_t total,
                                int dtype, hipStream_t stream);
 
+/* ---- Transformer-XL, evaluation with memory (csrc/transformer_xl.hip; LanguageModeling/Transformer-XL/pytorch/mem_transformer.py,
+ * utils/proj_adaptive_softmax.py) ------------------------------------------------------------------------------------------------
+ * All tensors 16-bit (DLE_F16 / DLE_BF16) unless said otherwise, 16-byte aligned; accumulation, softmax and the scale are fp32.
+ *
+ * dle_txl_rel_attention_fwd: RelPartialLearnableMultiHeadAttn.forward between qkv_net and o_net (mem_transformer.py:249-293, with
+ *   _rel_shift :210-223 and the masks of MemTransformerLM._forward :691-699) in ONE launch per layer and segment:
+ *     a_i = round16(float(q_i) + float(u)),  b_i = round16(float(q_i) + float(v))                  (u = r_w_bias, v = r_r_bias)
+ *     score(i,j)   = scale * ( a_i . K_j + b_i . r[i + mlen - j] )
+ *     allowed(i,j) = (i - shift < j) and (j <= i + mlen)
+ *     ctx_i        = round16( sum_j softmax_j(score(i,.) over the allowed j) * V_j )
+ *   q [B*qlen, ldq], rows batch-major, head h at columns h*64 (ldq lets it read the Q third of a [.., 3H] projection in place);
+ *   u, v [heads, 64]; kv a RING [B, cap, 2H], K in columns 0..H-1 and V in H..2H-1: logical key j (0 <= j < klen = mlen + qlen)
+ *   of batch element n lives at physical row (start + j) mod cap, the last qlen logical rows are the current segment's; r
+ *   [n_dist, H] indexed BY DISTANCE (row d = r_net(pos_emb(min(d, clamp_len))), n_dist >= klen); ctx [B*qlen, H].  shift =
+ *   qlen - (klen - mem_len - 1) under same_length when that is positive, any value >= qlen for "no lower bound".  Physical ring
+ *   rows outside the logical window never influence the result, whatever bits they hold.
+ *   Envelope: head_dim == 64, 1 <= qlen <= 512, 0 <= mlen, klen <= cap <= 4096, 0 <= start < cap, shift >= 1, every operand below
+ *   4 GiB; dle_txl_attention_supported(qlen, klen, head_dim) tells; anything else is -1 and a message, nothing launched.
+ *   dle_txl_attention_launch_count: launches by this process so far (tests).
+ * dle_txl_kv_append: the K and V thirds of the segment's projection qkv [B*qlen, ld >= 3H] -> ring rows (start + mlen + t) mod cap
+ *   (what `cat([mems, w])` followed by qkv_net recomputes in the reference, :239-247; _update_mems :652-682 is the ring's start).
+ * dle_rows_gather_scale: dst[dst_idx[r], :width] = round16(scale * float(src[src_idx[r], :width])) for r < rows; either int32 index
+ *   list may be NULL (= r).  The embedding lookup times sqrt(d_model) (AdaptiveEmbedding.forward :484-513) and the row gathers /
+ *   scatters of both adaptive layers (proj_adaptive_softmax.py:166-199).  width a multiple of 8; a row whose index is outside
+ *   [0, n_src_rows) / [0, n_dst_rows) is skipped; destination rows must be distinct.
+ * dle_row_nll: nll[pos[r]] (+)= logsumexp(logits[r, :n_classes]) - logits[r, target[r]] on fp32 logits [rows, ld]
+ *   (-log_softmax(..).gather(..), proj_adaptive_softmax.py:150-152, 179-199); pos int32 or NULL (= r), positions of one call
+ *   distinct; accumulate != 0 adds.  One workgroup per row, 1 <= n_classes <= 160003; a row whose target or position is out of
+ *   range writes nothing. */
+int dle_txl_attention_supported(int qlen, int klen, int head_dim);
+uint64_t dle_txl_attention_launch_count(void);
+int dle_txl_rel_attention_fwd(const void* q, int64_t ldq, const void* u, const void* v, const void* kv, const void* r, void* ctx,
+                              int B, int heads, int head_dim, int qlen, int mlen, int cap, int start, int n_dist, int shift,
+                              float scale, int dtype, hipStream_t stream);
+int dle_txl_kv_append(const void* qkv, int64_t ld, void* kv, int B, int H, int qlen, int mlen, int cap, int start, int dtype,
+                      hipStream_t stream);
+int dle_rows_gather_scale(const void* src, const int32_t* src_idx, void* dst, const int32_t* dst_idx, int64_t rows, int width,
+                          int64_t ld_src, int64_t ld_dst, int64_t n_src_rows, int64_t n_dst_rows, float scale, int dtype,
+                          hipStream_t stream);
+int dle_row_nll(const float* logits, int64_t ld, const int32_t* target, const int32_t* pos, float* nll, int64_t rows,
+                int n_classes, int64_t n_out, int accumulate, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
