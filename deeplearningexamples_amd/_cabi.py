@@ -86,6 +86,10 @@ _SIGS = {
     "dle_conv2d_grouped_fwd_affine": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
     "dle_se_gate": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "dle_se_apply": (c_int, [c_void_p] * 4 + [c_i64, c_int, c_int, c_int, c_int, c_void_p]),
+    "dle_dwconv2d_act_fwd": (c_int, [c_void_p] * 6 + [c_i64] + [c_int] * 9 + [c_void_p]),
+    "dle_dwconv2d_pool_bands": (c_int, [c_int] * 5),
+    "dle_se_gate_act": (c_int, [c_void_p, c_int, c_float] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "dle_silu_avgpool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dle_conv2d_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
     "dle_conv2d_wgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_i64, c_void_p]),
     "dle_nchw_to_nhwc": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),

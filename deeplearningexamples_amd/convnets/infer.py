@@ -257,3 +257,89 @@ class ResNeXtClassifier(ResNet50Classifier):
             target = target.to(self.dev)
         loss, _ = F.softmax_xent(logits, target, smoothing=0.0)
         return loss, logits
+
+
+class _MBConv:
+    """One MBConv block as the kernels read it."""
+    __slots__ = ("expand", "w_dw", "scale_dw", "shift_dw", "stride", "in_act", "se", "proj", "residual")
+
+
+class EfficientNetClassifier(ResNet50Classifier):
+    """EfficientNet-B0..B7 / wide-SE inference (models/efficientnet.py:175-310, :384-452) around the depthwise kernel
+    (functional.dwconv2d_act_fwd).  SiLU moves to the consumer: a unit the reference follows with SiLU runs
+    with relu=False and writes its BatchNorm output, rounded once; whoever reads that tensor applies the SiLU while staging it and
+    rounds the value to 16 bits, as the reference's SiLU writes a 16-bit tensor.  Per block: expand 1x1 (affine; absent at expansion
+    1), the depthwise unit (input SiLU, affine, SiLU, SE pool partials), se_gate_act (SiLU hidden layer), se_apply, project 1x1
+    (affine + residual where stride == 1 and in == out).  Stem: the 3x3 / 2 convolution on the 8-channel image; tail: features 1x1
+    (affine), SiLU + average pooling, fc.  efficientnet.EffNetArch.launch_count() launches: 83 for b0, 162 for b4."""
+
+    def __init__(self, model, dtype=torch.bfloat16, device=None, graphs=False):
+        """model: an efficientnet.EfficientNet (left untouched) or a state dict / checkpoint dict of any architecture of the family
+        (any device; `module.` prefixes and the published files' `layerN.` spelling allowed; original versus wide-SE is recognised
+        from the squeeze weights' shapes)."""
+        from . import efficientnet as E
+        if dtype == torch.float32:
+            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
+                             "recipes are not built)")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("EfficientNetClassifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        if not isinstance(model, E.EfficientNet):
+            state = E.remap_ngc(state_from_checkpoint(model))
+            dev = torch.device(device if device is not None else "cuda")
+            module = E.build(E.arch_from_state(state), num_classes=state["classifier.fc.weight"].shape[0], device=dev)
+            module.load_state_dict(state)
+            model = module
+        fc = model.classifier.fc
+        self.dev = fc.weight.device
+        self.dtype, self.graphs = dtype, bool(graphs)
+        self.num_classes = fc.weight.shape[0]
+        self.arch = model.arch
+        with torch.no_grad():
+            self.stem = self._cb(model.stem)
+            self.blocks = [self._block(blk, first=i == 0) for i, blk in enumerate(model.mbconv_blocks())]
+            self.features = self._cb(model.features)
+            self.fc_w16 = F.cast(fc.weight.data, dtype)
+            self.fc_bias = fc.bias.data.float().clone()
+        self._mean_std = None
+        self._graphs = {}
+
+    def _cb(self, seq):
+        """A conv + BatchNorm pair of the module tree -> _Unit, never with a ReLU: the SiLU behind it is its reader's."""
+        return self._unit(ConvBN(seq.conv, seq.bn, "conv", "bn", relu=False))
+
+    def _block(self, blk, first):
+        b = _MBConv()
+        b.expand = self._cb(blk.expand) if blk.expand is not None else None
+        # the depthwise unit applies the SiLU of the unit it reads: the expand unit's, or the stem's for the network's first block;
+        # a later block without an expand unit reads a projection, which has no activation
+        b.in_act = b.expand is not None or first
+        b.w_dw = F.pack_depthwise_weight(blk.depsep.conv.weight.data, self.dtype)
+        bn = blk.depsep.bn
+        b.scale_dw, b.shift_dw = fold_bn(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
+        b.stride = blk.stride
+        b.se = tuple(t.data.float().contiguous().clone() for t in (blk.se.squeeze.weight, blk.se.squeeze.bias, blk.se.expand.weight,
+                                                                   blk.se.expand.bias))
+        b.proj = self._cb(blk.proj)
+        b.residual = blk.residual
+        return b
+
+    def _forward(self, images):
+        if images.dtype == torch.uint8:
+            if self._mean_std is None:
+                from .dataloaders import IMAGENET_MEAN, IMAGENET_STD
+                self._mean_std = (torch.tensor(IMAGENET_MEAN, device=self.dev) * 255.0, torch.tensor(IMAGENET_STD, device=self.dev) * 255.0)
+            x = F.u8_nchw_normalize_nhwc(images, self._mean_std[0], self._mean_std[1], self.dtype, 8)
+        else:
+            x = F.nchw_to_nhwc(images, self.dtype, 8)
+        h = self._run(self.stem, x)
+        for b in self.blocks:
+            t = h if b.expand is None else self._run(b.expand, h)
+            t, pool = F.dwconv2d_act_fwd(t, b.w_dw, b.scale_dw, b.shift_dw, b.stride, in_act=b.in_act, out_act=True, pool=True)
+            gate = F.se_gate_act(pool, 1.0 / (t.shape[1] * t.shape[2]), *b.se, act="silu")
+            t = F.se_apply(t, gate, residual=None, relu=False)
+            h = self._run(b.proj, t, residual=h if b.residual else None)
+        pooled = F.silu_avgpool_fwd(self._run(self.features, h))
+        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
+                      out_dtype=torch.float32, bias=self.fc_bias)
+
+    eval_step = ResNeXtClassifier.eval_step

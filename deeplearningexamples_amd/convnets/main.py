@@ -204,6 +204,21 @@ def evaluate_resnext(args):
     state_from_checkpoint), the classifier of convnets/infer.py and the `validate` loop on its eval_step.  No trainer."""
     from . import resnext
     from .infer import ResNeXtClassifier, state_from_checkpoint
+
+    def make(device):
+        model = resnext.build(args.arch, num_classes=args.num_classes, last_bn_0_init=args.last_bn_0_init, device=device)
+        path = args.pretrained_from_file or args.resume
+        if path:
+            if not os.path.isfile(path):
+                raise SystemExit("=> no checkpoint found at '%s'" % path)
+            model.load_state_dict(state_from_checkpoint(torch.load(path, map_location=device, weights_only=False)))
+        return ResNeXtClassifier(model, dtype=torch.bfloat16 if args.amp_dtype == "bf16" else torch.float16)
+    return evaluate_classifier(args, make)
+
+
+def evaluate_classifier(args, make):
+    """The evaluation-only run of an inference-only architecture: make(device) -> a classifier of convnets/infer.py, then the
+    `validate` loop on its eval_step and the closing dllogger lines.  No trainer."""
     rank, world, local = init_from_env()
     device = torch.device("cuda", local)
     if args.seed is not None:
@@ -214,14 +229,7 @@ def evaluate_resnext(args):
         dllogger.init([dllogger.JSONStreamBackend(dllogger.Verbosity.VERBOSE, os.path.join(args.workspace, args.raport_file)),
                        dllogger.StdOutBackend(dllogger.Verbosity.DEFAULT)])
         dllogger.log(step="PARAMETER", data=vars(args))
-    model = resnext.build(args.arch, num_classes=args.num_classes, last_bn_0_init=args.last_bn_0_init, device=device)
-    path = args.pretrained_from_file or args.resume
-    if path:
-        if not os.path.isfile(path):
-            raise SystemExit("=> no checkpoint found at '%s'" % path)
-        model.load_state_dict(state_from_checkpoint(torch.load(path, map_location=device, weights_only=False)))
-    dtype = torch.bfloat16 if args.amp_dtype == "bf16" else torch.float16
-    clf = ResNeXtClassifier(model, dtype=dtype)
+    clf = make(device)
     get_val = get_synthetic_loader if args.data_backend == "synthetic" else get_pytorch_val_loader
     val_loader, _ = get_val(args.data, args.image_size, args.batch_size, args.num_classes, workers=args.workers,
                             memory_format=args.memory_format, prefetch_factor=args.prefetch, device=device, rank=rank, world=world,

@@ -746,6 +746,117 @@ def se_apply(t, gate, residual=None, relu=True, out=None):
     return out
 
 
+# ------------------------------------------------------------------ EfficientNet's MBConv block (csrc/efficientnet.hip)
+def dwconv2d_pool_bands(h, w, c, ksize, stride):
+    """G of dwconv2d_act_fwd's pool [N, G, C] for an [N, h, w, c] input (host only)."""
+    g = C.lib().dle_dwconv2d_pool_bands(int(h), int(w), int(c), int(ksize), int(stride))
+    if g < 0:
+        raise ValueError("dwconv2d_pool_bands: %s" % C.lib().dle_last_error().decode("utf-8", "replace"))
+    return g
+
+
+def dwconv2d_act_fwd(x, w, scale, shift, stride=1, in_act=False, out_act=False, pool=False, out=None):
+    """Depthwise k x k (k 3 or 5, pad k // 2, stride 1 or 2) inference unit in one launch:
+        y = round16(silu?(scale[c] * dwconv(a, w) + shift[c])),  a = round16(silu(x)) with in_act, x without.
+    x [N,H,W,C] 16-bit contiguous (C % 8 == 0), w [k,k,C] of x's dtype (pack_depthwise_weight), scale / shift fp32 [C].
+    pool: False -> returns y [N,P,Q,C]; True or a contiguous fp32 [N,G,C] tensor (G = dwconv2d_pool_bands) -> returns (y, pool), pool
+    holding the per-tile fp32 sums of the rounded y that se_gate_act folds.  Anything outside the envelope raises ValueError."""
+    name = "dwconv2d_act_fwd"
+    if x.dim() != 4 or w.dim() != 3:
+        raise ValueError("%s: x must be [N,H,W,C] and w [k,k,C]" % name)
+    n, h, wd, c = x.shape
+    k = w.shape[0]
+    if x.dtype not in _FP16:
+        raise ValueError("%s: 16-bit activations and weights only (got %s)" % (name, x.dtype))
+    if c < 8 or c % 8:
+        raise ValueError("%s: C must be a multiple of 8 (got %d)" % (name, c))
+    if k not in (3, 5) or tuple(w.shape) != (k, k, c):
+        raise ValueError("%s: w must be [k,k,C] with k 3 or 5 (got %s)" % (name, tuple(w.shape)))
+    if stride not in (1, 2):
+        raise ValueError("%s: stride 1 or 2 (got %s)" % (name, stride))
+    if w.dtype != x.dtype or not x.is_contiguous() or not w.is_contiguous() or h < 1 or wd < 1:
+        raise ValueError("%s: x must be NHWC-contiguous and w [k,k,C]-contiguous of x's dtype" % name)
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous():
+            raise ValueError("%s: scale / shift must be contiguous fp32 [C]" % name)
+    for t, what in ((x, "x"), (w, "w"), (scale, "scale"), (shift, "shift")):
+        if t.data_ptr() % 16:
+            raise ValueError("%s: %s must be 16-byte aligned" % (name, what))
+    p, q = _conv_out(h, wd, k, k, stride, k // 2)
+    if out is not None and (tuple(out.shape) != (n, p, q, c) or out.dtype != x.dtype or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("%s: out must be a contiguous, 16-byte aligned [N,P,Q,C] tensor of x's dtype" % name)
+    g = dwconv2d_pool_bands(h, wd, c, k, stride)
+    want_pool = pool is not False and pool is not None
+    if isinstance(pool, torch.Tensor) and (tuple(pool.shape) != (n, g, c) or pool.dtype != torch.float32 or not pool.is_contiguous()
+                                           or pool.data_ptr() % 16):
+        raise ValueError("%s: pool must be a contiguous, 16-byte aligned fp32 [N,G,C] = %s tensor (got %s %s)"
+                         % (name, (n, g, c), pool.dtype, tuple(pool.shape)))
+    C.require_cuda(x, w, scale, shift, out, pool if isinstance(pool, torch.Tensor) else None)
+    if out is None:
+        out = torch.empty((n, p, q, c), dtype=x.dtype, device=x.device)
+    if want_pool and not isinstance(pool, torch.Tensor):
+        pool = torch.empty((n, g, c), dtype=torch.float32, device=x.device)
+    pt = pool if want_pool else None
+    C.annotate(flops=2.0 * n * p * q * c * k * k, tag="dwconv %dx%dx%dx%d k%d s%d" % (n, h, wd, c, k, stride),
+               bytes=float(x.numel() + w.numel() + out.numel()) * 2 + (pt.numel() * 4 if want_pool else 0))
+    C.call("dle_dwconv2d_act_fwd", C.ptr(x), C.ptr(w), C.ptr(out), C.ptr(scale), C.ptr(shift), C.ptr(pt),
+           pt.numel() * 4 if want_pool else 0, n, h, wd, c, k, stride, int(bool(in_act)), int(bool(out_act)), C.dt(x), C.stream())
+    return (out, pt) if want_pool else out
+
+
+SE_GATE_ACT_MAX_C_PLUS_S = 16384          # DLE_SE_GATE_ACT_MAX_C_PLUS_S
+
+
+def se_gate_act(pool, inv_hw, w1, b1, w2, b2, act="silu", out=None):
+    """Squeeze-and-excitation gate from pool partials: sigmoid(w2 @ f(w1 @ (inv_hw * sum_g pool[:, g]) + b1) + b2), f = SiLU
+    (act "silu") or ReLU ("relu"), all in fp32.  pool [N,G,C] (dwconv2d_act_fwd) or [N,C]; w1 [S,C], b1 [S], w2 [C,S], b2 [C]
+    contiguous fp32, any S >= 1 with C + S <= 16384 -> gate [N,C] fp32."""
+    name = "se_gate_act"
+    if act not in ("silu", "relu"):
+        raise ValueError("%s: act must be 'silu' or 'relu' (got %r)" % (name, act))
+    if pool.dim() not in (2, 3) or pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise ValueError("%s: pool must be a contiguous fp32 [N,G,C] or [N,C] tensor" % name)
+    n, c = pool.shape[0], pool.shape[-1]
+    g = pool.shape[1] if pool.dim() == 3 else 1
+    if c < 8 or c % 8 or g < 1:
+        raise ValueError("%s: C must be a multiple of 8 and G >= 1 (got C %d, G %d)" % (name, c, g))
+    s = w1.shape[0] if w1.dim() == 2 else 0
+    for v, shape in ((w1, (s, c)), (b1, (s,)), (w2, (c, s)), (b2, (c,))):
+        if v.dtype != torch.float32 or tuple(v.shape) != shape or not v.is_contiguous() or s < 1:
+            raise ValueError("%s: weights must be contiguous fp32 w1 [S,C], b1 [S], w2 [C,S], b2 [C]" % name)
+    if c + s > SE_GATE_ACT_MAX_C_PLUS_S:
+        raise ValueError("%s: C + S = %d: the mean and the hidden vector live in LDS, C + S <= %d" % (name, c + s, SE_GATE_ACT_MAX_C_PLUS_S))
+    if out is not None and (tuple(out.shape) != (n, c) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous fp32 [N,C] tensor" % name)
+    C.require_cuda(pool, w1, b1, w2, b2, out)
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=pool.device)
+    C.call("dle_se_gate_act", C.ptr(pool), g, float(inv_hw), C.ptr(w1), C.ptr(b1), C.ptr(w2), C.ptr(b2), C.ptr(out), n, c, s,
+           1 if act == "silu" else 0, C.stream())
+    return out
+
+
+def silu_avgpool_fwd(x, out=None):
+    """y[n,c] = round16(mean_hw round16(silu(x[n,hw,c]))), the fp32 sum in a fixed order.  x [N,H,W,C] or [N,HW,C] 16-bit contiguous
+    (C % 8 == 0) -> y [N,C] of x's dtype."""
+    name = "silu_avgpool_fwd"
+    if x.dim() not in (3, 4) or not x.is_contiguous() or x.dtype not in _FP16:
+        raise ValueError("%s: x must be a contiguous 16-bit [N,H,W,C] or [N,HW,C] tensor" % name)
+    n, c = x.shape[0], x.shape[-1]
+    if c < 8 or c % 8:
+        raise ValueError("%s: C must be a multiple of 8 (got %d)" % (name, c))
+    hw = x.numel() // max(n * c, 1)
+    if hw < 1 or x.data_ptr() % 16:
+        raise ValueError("%s: x must hold at least one pixel and be 16-byte aligned" % name)
+    if out is not None and (tuple(out.shape) != (n, c) or out.dtype != x.dtype or not out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous [N,C] tensor of x's dtype" % name)
+    C.require_cuda(x, out)
+    if out is None:
+        out = torch.empty((n, c), dtype=x.dtype, device=x.device)
+    C.call("dle_silu_avgpool_fwd", C.ptr(x), C.ptr(out), n, hw, c, C.dt(x), C.stream())
+    return out
+
+
 def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, addend=None, out=None):
     """dy [N,P,Q,Ko], w [Ko,R,S,C] -> dx [N,H,W,C] (+ addend)."""
     C.require_cuda(dy, w, addend, out)
@@ -1941,7 +2052,12 @@ def fp_unpack_mel(x, bias, cu_seqlens, t_pad, out=None):
 # ------------------------------------------------------------------ QuartzNet on packed utterances (csrc/quartznet.hip)
 def pack_depthwise_weight(w, dtype):
     """torch's depthwise Conv1d weight [C, 1, ksize] (any device / float dtype) -> the [ksize, C] 16-bit tensor tcs_conv1d_packed_fwd
-    reads: a tap's channels are contiguous (one rounding per element)."""
+    reads: a tap's channels are contiguous (one rounding per element).  A depthwise Conv2d weight [C, 1, k, k] -> the [k, k, C]
+    tensor dwconv2d_act_fwd reads, likewise."""
+    if w.dim() == 4 and w.shape[1] == 1 and w.shape[2] == w.shape[3]:
+        if dtype not in _FP16:
+            raise ValueError("pack_depthwise_weight: dtype must be torch.float16 or torch.bfloat16")
+        return w.detach()[:, 0].permute(1, 2, 0).to(dtype).contiguous()
     if w.dim() != 3 or w.shape[1] != 1:
         raise ValueError("pack_depthwise_weight: expected a [C, 1, ksize] weight (got %s)" % (tuple(w.shape),))
     if dtype not in _FP16:

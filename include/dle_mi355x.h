@@ -232,6 +232,47 @@ int dle_se_gate(const void* t, const float* w1, const float* b1, const float* w2
                 int N, int HW, int C, int S, int dtype, hipStream_t stream);
 int dle_se_apply(const void* t, const float* gate, const void* residual, void* y,
                  int64_t N, int HW, int C, int dtype, int relu, hipStream_t stream);
+/* Inference, EfficientNet's MBConv block (csrc/efficientnet.hip): the depthwise k x k convolution with the evaluation-mode
+ * BatchNorm, the SiLU of the unit BEFORE it (applied to the input while it is staged), its own SiLU and the squeeze-and-excitation
+ * pooling in one launch.  Replaces, under model.eval(),
+ *   Classification/ConvNets/image_classification/models/common.py:31-79 (LayerBuilder.conv with groups == in_planes, padding
+ *   int((k-1)/2), no bias -> BatchNorm2d -> SiLU), :123-128 (nn.SiLU), models/efficientnet.py:384-452 (MBConvBlock.depsep)
+ *   a[n,h,w,c]  = in_act ? round16(silu(float(x[n,h,w,c]))) : x[n,h,w,c]                     (0 outside the image)
+ *   acc         = sum_{r,s} float(w[r,s,c]) * float(a[n, p*stride + r - k/2, q*stride + s - k/2, c])          fp32 fmaf
+ *   y[n,p,q,c]  = round16( out_act ? silu(v) : v ),   v = fmaf(scale[c], acc, shift[c])
+ *   pool[n,g,c] = fp32 sum of float(y[n,p,q,c]) over the output pixels of tile g                 (pool == NULL: not written)
+ *   P = (H + 2 (k/2) - k) / stride + 1, likewise Q;   silu(v) = v / (1 + expf(-v)), accurate expf, true division (v < -88, where
+ *   expf(-v) overflows: the same quotient as v * expf(v))
+ * x, y NHWC 16-bit; w [k][k][C] 16-bit = torch's [C,1,k,k] permuted (functional.pack_depthwise_weight); scale / shift fp32 [C].
+ * Tiling: a workgroup owns DLE_DWCONV_TILE_ROWS x DLE_DWCONV_TILE_COLS output pixels of one image and DLE_DWCONV_CHUNK channels;
+ * the input tile with its halo sits in LDS after the input SiLU (at most 88,320 bytes of dynamic LDS at k 5 / stride 2, opted in
+ * per device).  Pool "bands" are those tiles, row-major: G = ceil(P / TILE_ROWS) * ceil(Q / TILE_COLS) =
+ * dle_dwconv2d_pool_bands(H, W, C, ksize, stride) (host only; -1 on a bad argument).  Each partial is written once by one
+ * workgroup (no atomics) and summed over its pixels in a fixed order: bitwise reproducible.  pool_bytes >= N * G * C * 4.
+ * Envelope: C % 8 == 0, ksize in {3, 5}, stride in {1, 2}, any H, W >= 1, in_act / out_act in {0, 1}, every operand 16-byte
+ * aligned, each tensor below 2^31 elements; anything else is an argument error (-1), never a fallback.  No allocation, no
+ * synchronisation (graph capturable). */
+#define DLE_DWCONV_TILE_ROWS 8
+#define DLE_DWCONV_TILE_COLS 16
+#define DLE_DWCONV_CHUNK 64
+int dle_dwconv2d_act_fwd(const void* x, const void* w, void* y, const float* scale, const float* shift, float* pool,
+                         int64_t pool_bytes, int N, int H, int W, int C, int ksize, int stride, int in_act, int out_act,
+                         int dtype, hipStream_t stream);
+int dle_dwconv2d_pool_bands(int H, int W, int C, int ksize, int stride);
+/* The squeeze-and-excitation gate of an MBConv block from the pool partials of dle_dwconv2d_act_fwd.  Replaces, under
+ * model.eval(), models/common.py:146-164 and :231-250 (SequentialSqueezeAndExcitation._attention with the SiLU activation)
+ *   mean[n,c] = inv_hw * (pool[n,0,c] + pool[n,1,c] + ... + pool[n,G-1,c], in this order)
+ *   gate[n,c] = sigmoid(b2[c] + sum_s w2[c,s] * f(b1[s] + sum_c' w1[s,c'] * mean[n,c'])),   f = SiLU (act 1) or ReLU (act 0)
+ * pool [N,G,C], w1 [S,C], b1 [S], w2 [C,S], b2 [C], gate [N,C], all fp32 -- both products in fp32 on fp32 weights (the
+ * reference's autocast runs them in fp16).  Any S >= 1; the mean and the hidden vector live in LDS (64 KiB, no opt-in), so
+ * C + S <= DLE_SE_GATE_ACT_MAX_C_PLUS_S; C % 8 == 0.  No allocation, no synchronisation.  dle_se_gate is unchanged. */
+#define DLE_SE_GATE_ACT_MAX_C_PLUS_S 16384
+int dle_se_gate_act(const float* pool, int G, float inv_hw, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* gate, int N, int C, int S, int act, hipStream_t stream);
+/* The features unit's SiLU with AdaptiveAvgPool2d(1) behind it (models/efficientnet.py:289-310, common.py:123-128):
+ *   y[n,c] = round16( (1/HW) * sum_hw float(round16(silu(float(x[n,hw,c])))) ),  the fp32 sum in a fixed order
+ * x [N,HW,C] 16-bit (16-byte aligned), y [N,C] 16-bit, C % 8 == 0, x below 2^31 elements.  No allocation, no synchronisation. */
+int dle_silu_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int dtype, hipStream_t stream);
 int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int R, int S,
                      int stride, int pad, int dtype, int splitk, int accumulate, void* workspace,
                      int64_t workspace_bytes, hipStream_t stream);
