@@ -90,6 +90,10 @@ _SIGS = {
     "dle_dwconv2d_pool_bands": (c_int, [c_int] * 5),
     "dle_se_gate_act": (c_int, [c_void_p, c_int, c_float] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "dle_silu_avgpool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dle_ssd_decode_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                   c_int, c_void_p]),
+    "dle_ssd_nms_fwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_float, c_int, c_void_p]),
+    "dle_ssd_select_fwd": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p]),
     "dle_conv2d_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
     "dle_conv2d_wgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_i64, c_void_p]),
     "dle_nchw_to_nhwc": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),

@@ -3,6 +3,7 @@
 Every function here launches hand-written HIP kernels from libdle_mi355x.so on the current
 torch stream; there is no eager fallback.  torch is used for memory, streams and autograd plumbing.
 """
+import ctypes
 import os
 
 import torch
@@ -855,6 +856,92 @@ def silu_avgpool_fwd(x, out=None):
         out = torch.empty((n, c), dtype=x.dtype, device=x.device)
     C.call("dle_silu_avgpool_fwd", C.ptr(x), C.ptr(out), n, hw, c, C.dt(x), C.stream())
     return out
+
+
+# ------------------------------------------------------------------ SSD300 detection post-processing (csrc/ssd.hip)
+SSD_MAX_MAPS, SSD_MAX_KEEP, SSD_MAX_BOXES = 8, 256, 16384          # DLE_SSD_MAX_MAPS / _KEEP / _BOXES
+
+
+def ssd_decode(heads, geom, dboxes_xywh, num_labels, scale_xy=0.1, scale_wh=0.2):
+    """Head outputs -> (boxes [N,B,4] fp32 ltrb, probs [N,L,B] fp32 softmax, class-major).  heads: one contiguous 16-bit NHWC tensor
+    [N, fs, fs, pitch] per feature map; geom: per map (nd, loc, conf) -- channels [loc, loc + 4 nd) are the location part and
+    [conf, conf + L nd) the confidence part, laid out as the reference's NCHW heads (channel c = coordinate or label c // nd of
+    anchor c % nd; box index a*fs*fs + h*fs + w inside the map).  dboxes_xywh: contiguous fp32 [B,4]."""
+    name = "ssd_decode"
+    if not 1 <= len(heads) <= SSD_MAX_MAPS or len(geom) != len(heads):
+        raise ValueError("%s: 1..%d feature maps with one (nd, loc, conf) each" % (name, SSD_MAX_MAPS))
+    h0 = heads[0]
+    if h0.dtype not in _FP16:
+        raise ValueError("%s: 16-bit head outputs only (got %s)" % (name, h0.dtype))
+    n, table, b = h0.shape[0], [], 0
+    for t, (nd, loc, conf) in zip(heads, geom):
+        if t.dim() != 4 or t.shape[0] != n or t.shape[1] != t.shape[2] or t.dtype != h0.dtype or not t.is_contiguous():
+            raise ValueError("%s: every head must be a contiguous [N, fs, fs, pitch] tensor of one dtype" % name)
+        table += [int(t.shape[1]), int(nd), int(t.shape[3]), int(loc), int(conf)]
+        b += int(nd) * int(t.shape[1]) ** 2
+    if dboxes_xywh.dtype != torch.float32 or tuple(dboxes_xywh.shape) != (b, 4) or not dboxes_xywh.is_contiguous():
+        raise ValueError("%s: dboxes_xywh must be a contiguous fp32 [B,4] = [%d,4] tensor" % (name, b))
+    C.require_cuda(dboxes_xywh, *heads)
+    boxes = torch.empty((n, b, 4), dtype=torch.float32, device=h0.device)
+    probs = torch.empty((n, int(num_labels), b), dtype=torch.float32, device=h0.device)
+    ptrs = (ctypes.c_void_p * len(heads))(*[t.data_ptr() for t in heads])
+    g = (ctypes.c_int * len(table))(*table)
+    C.call("dle_ssd_decode_fwd", ptrs, g, len(heads), C.ptr(dboxes_xywh), C.ptr(boxes), C.ptr(probs), n, b, int(num_labels),
+           float(scale_xy), float(scale_wh), C.dt(h0), C.stream())
+    return boxes, probs
+
+
+def _ssd_boxes_probs(name, boxes, probs):
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.dtype != torch.float32 or not boxes.is_contiguous():
+        raise ValueError("%s: boxes must be a contiguous fp32 [N,B,4] tensor" % name)
+    if probs is not None and (probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous()
+                              or probs.shape[0] != boxes.shape[0] or probs.shape[2] != boxes.shape[1]):
+        raise ValueError("%s: probs must be a contiguous fp32 [N,L,B] tensor" % name)
+
+
+def ssd_nms(boxes, probs, criteria=0.5, threshold=0.05, max_num=200):
+    """Greedy per-class non-maximum suppression, one workgroup per (image, label >= 1).  boxes [N,B,4] fp32 ltrb, probs [N,L,B] fp32
+    -> (kept_idx [N,L-1,max_num] int32, best first, -1 past the count; kept_score [N,L-1,max_num] fp32; kept_count [N,L-1] int32).
+    Candidates: prob > threshold, the max_num best (ties: lower box index first); a candidate survives a kept one only if
+    iou < criteria (a NaN suppresses)."""
+    name = "ssd_nms"
+    _ssd_boxes_probs(name, boxes, probs)
+    n, l, b = probs.shape
+    C.require_cuda(boxes, probs)
+    max_num = int(max_num)
+    m = max(max_num, 1)
+    kept_idx = torch.empty((n, max(l - 1, 0), m), dtype=torch.int32, device=boxes.device)
+    kept_score = torch.empty((n, max(l - 1, 0), m), dtype=torch.float32, device=boxes.device)
+    kept_count = torch.empty((n, max(l - 1, 0)), dtype=torch.int32, device=boxes.device)
+    C.call("dle_ssd_nms_fwd", C.ptr(boxes), C.ptr(probs), C.ptr(kept_idx), C.ptr(kept_score), C.ptr(kept_count), n, b, l,
+           float(threshold), float(criteria), max_num, C.stream())
+    return kept_idx, kept_score, kept_count
+
+
+def ssd_select(boxes, kept_idx, kept_score, kept_count, max_output=200):
+    """The max_output best of an image's kept candidates, best first (ties: lower label, then lower box index)
+    -> (det_boxes [N,max_output,4] fp32, det_label [N,max_output] int32 (1..L-1), det_score fp32, det_idx int32 (the default-box
+    index), det_count [N] int32); rows past the count are zero."""
+    name = "ssd_select"
+    _ssd_boxes_probs(name, boxes, None)
+    n, b = boxes.shape[:2]
+    if (kept_idx.dim() != 3 or kept_idx.dtype != torch.int32 or kept_score.dtype != torch.float32 or kept_idx.shape != kept_score.shape
+            or kept_count.dtype != torch.int32 or tuple(kept_count.shape) != tuple(kept_idx.shape[:2]) or kept_idx.shape[0] != n
+            or not (kept_idx.is_contiguous() and kept_score.is_contiguous() and kept_count.is_contiguous())):
+        raise ValueError("%s: kept_idx int32 / kept_score fp32 [N,L-1,max_num] and kept_count int32 [N,L-1], contiguous (ssd_nms)" % name)
+    C.require_cuda(boxes, kept_idx, kept_score, kept_count)
+    lm1, max_num = kept_idx.shape[1:]
+    max_output = int(max_output)
+    m = max(max_output, 1)
+    dev = boxes.device
+    det_boxes = torch.empty((n, m, 4), dtype=torch.float32, device=dev)
+    det_label = torch.empty((n, m), dtype=torch.int32, device=dev)
+    det_score = torch.empty((n, m), dtype=torch.float32, device=dev)
+    det_idx = torch.empty((n, m), dtype=torch.int32, device=dev)
+    det_count = torch.empty((n,), dtype=torch.int32, device=dev)
+    C.call("dle_ssd_select_fwd", C.ptr(boxes), C.ptr(kept_idx), C.ptr(kept_score), C.ptr(kept_count), C.ptr(det_boxes),
+           C.ptr(det_label), C.ptr(det_score), C.ptr(det_idx), C.ptr(det_count), n, b, lm1 + 1, max_num, max_output, C.stream())
+    return det_boxes, det_label, det_score, det_idx, det_count
 
 
 def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, addend=None, out=None):

@@ -273,6 +273,53 @@ int dle_se_gate_act(const float* pool, int G, float inv_hw, const float* w1, con
  *   y[n,c] = round16( (1/HW) * sum_hw float(round16(silu(float(x[n,hw,c])))) ),  the fp32 sum in a fixed order
  * x [N,HW,C] 16-bit (16-byte aligned), y [N,C] 16-bit, C % 8 == 0, x below 2^31 elements.  No allocation, no synchronisation. */
 int dle_silu_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int dtype, hipStream_t stream);
+/* Inference, SSD300 detection post-processing (csrc/ssd.hip): three launches, fixed-size outputs, no host read.
+ *
+ * dle_ssd_decode_fwd: head outputs -> boxes and class probabilities.  Replaces Detection/SSD/ssd/model.py:108-115
+ * (SSD300.bbox_view) and ssd/utils.py:127-159 (Encoder.scale_back_batch).
+ *   heads[m] (a HOST array of nmaps <= DLE_SSD_MAX_MAPS device pointers): the 16-bit NHWC head tensor [N, fs, fs, pitch] of map m;
+ *   geom (a HOST array of 5 ints per map): fs, nd, pitch, loc, conf -- channels [loc, loc + 4 nd) are the location part, channels
+ *   [conf, conf + L nd) the confidence part (both inside the pitch; what else the pitch holds is not read).
+ *   INDEX RULE.  The reference reshapes the NCHW head output [N, nd*4, H, W] to [N, 4, nd*H*W] (and [N, nd*L, H, W] to
+ *   [N, L, nd*H*W]), so channel c of the location part is coordinate c / nd of anchor c % nd, channel c of the confidence part is
+ *   label c / nd of anchor c % nd, and the box of (anchor a, pixel h, w) has index a*H*W + h*W + w inside its map; the maps follow
+ *   each other in table order, B = sum nd * fs * fs.
+ *   fp32, every operation rounded on its own (no contraction), as the reference after .float():
+ *     x = (scale_xy * loc_x) * d_w + d_x   (y likewise)      w = expf(scale_wh * loc_w) * d_w   (h likewise)
+ *     boxes[n,b] = (x - 0.5 w, y - 0.5 h, x + 0.5 w, y + 0.5 h)       probs[n,l,b] = expf(c_l - max_l c) / sum_l expf(c_l - max_l c)
+ *   dboxes_xywh [B,4] fp32 (16-byte aligned); boxes [N,B,4] fp32; probs [N,L,B] fp32, class-major (dle_ssd_nms_fwd reads rows).
+ *   loc == 0 returns d_xy -+ 0.5 d_wh exactly.  L >= 2, B < 2^24, N * L * B < 2^31.
+ *
+ * dle_ssd_nms_fwd: one workgroup per (image, label 1..L-1).  Replaces the body of the class loop of Encoder.decode_single
+ * (ssd/utils.py:179-209) with calc_iou_tensor (utils.py:32-66).
+ *   candidates: the boxes with probs[n,l,b] > threshold (the reference: 0.05); the max_num best are kept (the reference: 200),
+ *   best = higher probability, then LOWER box index (the reference's sort leaves the order of equal scores open; this is the rule
+ *   here); greedy from the best downwards: a candidate survives a kept one only if iou < criteria -- written !(iou < criteria)
+ *   suppresses, so a NaN (a zero-area box against itself, 0/0) suppresses, as the reference's boolean index drops it.
+ *   iou: calc_iou_tensor's fp32 operations in its order -- max, min, subtract, clamp at 0, multiply, the two areas,
+ *   (area1 + area2) - intersect, a correctly rounded division -- without contraction: on the same fp32 boxes and scores the kept
+ *   set is the reference's bit for bit.
+ *   kept_idx [N,L-1,max_num] int32 (box indices, best first; -1 past the count), kept_score [N,L-1,max_num] fp32 (0 past the
+ *   count), kept_count [N,L-1] int32.  1 <= max_num <= DLE_SSD_MAX_KEEP, 1 <= B <= DLE_SSD_MAX_BOXES (the candidates' 64-bit keys are
+ *   sorted in LDS: 8 * pow2(B) + 14,368 bytes, opted in per device), boxes 16-byte aligned.  No atomics: deterministic.
+ *
+ * dle_ssd_select_fwd: one workgroup per image.  Replaces the tail of decode_single (utils.py:211-221).
+ *   the max_output best of all kept candidates, best first: higher score, then lower label, then lower box index.
+ *   det_boxes [N,max_output,4] fp32 (16-byte aligned), det_label (1..L-1), det_score, det_idx (the default-box index)
+ *   [N,max_output], det_count [N]; rows past the count are zero.  max_output <= DLE_SSD_MAX_KEEP and
+ *   (L - 1) * min(max_num, max_output) <= DLE_SSD_MAX_BOXES (only the first max_output entries of a class can be selected; they
+ *   are sorted in LDS).
+ * All three: a bad argument returns -1 without a launch; no allocation, no synchronisation (graph capturable). */
+#define DLE_SSD_MAX_MAPS 8
+#define DLE_SSD_MAX_KEEP 256
+#define DLE_SSD_MAX_BOXES 16384
+int dle_ssd_decode_fwd(const void* const* heads, const int* geom, int nmaps, const float* dboxes_xywh, float* boxes, float* probs,
+                       int N, int B, int L, float scale_xy, float scale_wh, int dtype, hipStream_t stream);
+int dle_ssd_nms_fwd(const float* boxes, const float* probs, int* kept_idx, float* kept_score, int* kept_count, int N, int B, int L,
+                    float threshold, float criteria, int max_num, hipStream_t stream);
+int dle_ssd_select_fwd(const float* boxes, const int* kept_idx, const float* kept_score, const int* kept_count, float* det_boxes,
+                       int* det_label, float* det_score, int* det_idx, int* det_count, int N, int B, int L, int max_num,
+                       int max_output, hipStream_t stream);
 int dle_conv2d_wgrad(const void* dy, const void* x, float* dw, int N, int H, int W, int C, int Ko, int R, int S,
                      int stride, int pad, int dtype, int splitk, int accumulate, void* workspace,
                      int64_t workspace_bytes, hipStream_t stream);
