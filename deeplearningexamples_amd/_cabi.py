@@ -264,6 +264,13 @@ _SIGS = {
     "dle_txl_kv_append": (c_int, [c_void_p, c_i64, c_void_p] + [c_int] * 7 + [c_void_p]),
     "dle_rows_gather_scale": (c_int, [c_void_p] * 4 + [c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_float, c_int, c_void_p]),
     "dle_row_nll": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p]),
+    "dle_tft_grn_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64] +
+                        [c_void_p] * 9 + [c_float, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p]),
+    "dle_tft_vsn_fwd": (c_int, [c_void_p, c_i64, c_int] * 3 + [c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                                                c_i64, c_i64, c_i64, c_void_p, c_i64, c_int, c_float, c_int, c_void_p]),
+    "dle_tft_lstm_fwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p,
+                                 c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dle_tft_attention_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
 }
 
 _lib = None

@@ -2433,3 +2433,248 @@ def row_nll(logits, target, nll, pos=None, n_classes=None, accumulate=False):
     C.call("dle_row_nll", C.ptr(logits), logits.stride(0), C.ptr(target), C.ptr(pos), C.ptr(nll), rows, n_classes, nll.numel(),
            int(bool(accumulate)), C.stream())
     return nll
+
+
+# ---- Temporal Fusion Transformer inference (csrc/tft.hip) ---------------------------------------------------------------------
+TFT_HIDDEN = 128
+TFT_MAX_VARS = 8
+TFT_ROW_TILE = 32            # rows per workgroup of the GRN / VSN kernels, batch rows per workgroup of the LSTM
+
+
+def _tft_rows16(name, t, what):
+    if t.dtype not in _FP16 or t.dim() != 2 or t.shape[1] != TFT_HIDDEN or t.stride(1) != 1 or t.stride(0) % 8 or \
+            (t.shape[0] > 1 and t.stride(0) < TFT_HIDDEN):
+        raise ValueError("%s: %s must be 16-bit [rows, 128] with unit inner stride and a row pitch that is a multiple of 8" % (name, what))
+
+
+def _tft_w16(name, t, shape, dtype, what):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor %s" % (name, what, dtype, list(shape)))
+
+
+def tft_grn_pack(grn, dtype, device):
+    """The parameters of one reference GRN (or of a GLU + LayerNorm pair given as {'glu': .., 'ln': ..}) as the kernel takes them:
+    16-bit weights [out][in], fp32 biases and LayerNorm parameters.  `grn` maps the reference's parameter names to tensors."""
+    def w(k):
+        return grn[k].detach().to(device=device, dtype=dtype).contiguous()
+
+    def f(k):
+        return grn[k].detach().to(device=device, dtype=torch.float32).contiguous()
+    p = {"wg": w("glu.lin.weight"), "bg": f("glu.lin.bias"), "gamma": f("layer_norm.ln.weight"), "beta": f("layer_norm.ln.bias")}
+    if "lin_a.weight" in grn:
+        p.update(wa=w("lin_a.weight"), ba=f("lin_a.bias"), wi=w("lin_i.weight"), bi=f("lin_i.bias"))
+        if "lin_c.weight" in grn:
+            p["wc"] = w("lin_c.weight")
+    return p
+
+
+def tft_grn_fwd(x, p, ctx=None, rows_per_ctx=1, res=None, res_rows_per_batch=0, x_index=None, wq=None, bq=None, eps=1e-3,
+                want_out=True, out=None):
+    """One gated residual network on x [rows, 128] (or on the rows x[x_index]), parameters from tft_grn_pack.  ctx [batch, 128]
+    with rows_per_ctx rows of x per context row.  Without 'wa' in p: gate mode, GLU(x) + res -> LayerNorm; res is [rows, 128] or,
+    with res_rows_per_batch, a [batch, steps, 128] tensor whose LAST res_rows_per_batch steps of every batch element are the rows.
+    wq [Q, 128] / bq [Q] fp32: also returns the fp32 [rows, Q] projection of the unrounded output.  Returns out, (out, q) or q."""
+    name = "tft_grn_fwd"
+    C.require_cuda(x, ctx, res, x_index, wq, bq, out)
+    _tft_rows16(name, x, "x")
+    dtype = x.dtype
+    gate = "wa" not in p
+    rows = x.shape[0] if x_index is None else x_index.numel()
+    if x_index is not None and (x_index.dtype != torch.int32 or x_index.dim() != 1 or not x_index.is_contiguous()):
+        raise ValueError("%s: x_index must be a contiguous int32 vector" % name)
+    _tft_w16(name, p["wg"], (2 * TFT_HIDDEN, TFT_HIDDEN), dtype, "wg")
+    _fp_f32(name, p["bg"], (2 * TFT_HIDDEN,), "bg")
+    _fp_f32(name, p["gamma"], (TFT_HIDDEN,), "gamma")
+    _fp_f32(name, p["beta"], (TFT_HIDDEN,), "beta")
+    res_ptr, ldr, res_bs = 0, 0, 0
+    if gate:
+        if res is None or ctx is not None:
+            raise ValueError("%s: gate mode takes a residual and no context" % name)
+        if res_rows_per_batch:
+            if res.dtype != dtype or res.dim() != 3 or res.shape[2] != TFT_HIDDEN or not res.is_contiguous() or \
+                    res.shape[1] < res_rows_per_batch or res.shape[0] * res_rows_per_batch != rows:
+                raise ValueError("%s: res must be a contiguous [rows / %d, steps >= %d, 128] tensor" % (name, res_rows_per_batch, res_rows_per_batch))
+            res_ptr = res.data_ptr() + (res.shape[1] - res_rows_per_batch) * TFT_HIDDEN * res.element_size()
+            ldr, res_bs = TFT_HIDDEN, res.shape[1] * TFT_HIDDEN
+        else:
+            _tft_rows16(name, res, "res")
+            if res.dtype != dtype or res.shape[0] != rows:
+                raise ValueError("%s: res must have the rows and the type of x" % name)
+            res_ptr, ldr = res.data_ptr(), res.stride(0) if rows > 1 else TFT_HIDDEN
+    else:
+        if res is not None:
+            raise ValueError("%s: the residual of the full network is its input" % name)
+        for k in ("wa", "wi"):
+            _tft_w16(name, p[k], (TFT_HIDDEN, TFT_HIDDEN), dtype, k)
+        _fp_f32(name, p["ba"], (TFT_HIDDEN,), "ba")
+        _fp_f32(name, p["bi"], (TFT_HIDDEN,), "bi")
+        if ctx is not None:
+            if "wc" not in p:
+                raise ValueError("%s: this network has no lin_c" % name)
+            _tft_w16(name, p["wc"], (TFT_HIDDEN, TFT_HIDDEN), dtype, "wc")
+            _tft_rows16(name, ctx, "ctx")
+            if ctx.dtype != dtype or rows_per_ctx < 1 or ctx.shape[0] * rows_per_ctx < rows:
+                raise ValueError("%s: ctx has %d rows for %d rows of x at %d rows per context" % (name, ctx.shape[0], rows, rows_per_ctx))
+    q = None
+    if wq is not None:
+        nq = wq.shape[0]
+        if not 1 <= nq <= 8:
+            raise ValueError("%s: 1 to 8 quantiles (got %d)" % (name, nq))
+        _fp_f32(name, wq, (nq, TFT_HIDDEN), "wq")
+        _fp_f32(name, bq, (nq,), "bq")
+        q = torch.empty((rows, nq), dtype=torch.float32, device=x.device)
+    if want_out or q is None:
+        out = _fp_out(name, out, (rows, TFT_HIDDEN), dtype, x.device)
+    else:
+        out = None
+    C.annotate(flops=2.0 * rows * TFT_HIDDEN * TFT_HIDDEN * (2 if gate else 4 + (ctx is not None)), tag="tft_grn %d%s" % (rows, " gate" if gate else ""))
+    C.call("dle_tft_grn_fwd", C.ptr(x), x.stride(0) if x.shape[0] > 1 else TFT_HIDDEN, C.ptr(x_index), x.shape[0] if x_index is not None else 0,
+           C.ptr(ctx), (ctx.stride(0) if ctx.shape[0] > 1 else TFT_HIDDEN) if ctx is not None else 0, int(rows_per_ctx),
+           res_ptr, ldr, int(res_rows_per_batch), res_bs,
+           C.ptr(p.get("wa")), C.ptr(p.get("ba")), C.ptr(p.get("wc")) if ctx is not None else 0, C.ptr(p.get("wi")), C.ptr(p.get("bi")),
+           C.ptr(p["wg"]), C.ptr(p["bg"]), C.ptr(p["gamma"]), C.ptr(p["beta"]), float(eps), C.ptr(out), TFT_HIDDEN,
+           C.ptr(wq), C.ptr(bq), C.ptr(q), q.shape[1] if q is not None else 0, rows, TFT_HIDDEN, C.dt(dtype), C.stream())
+    if q is None:
+        return out
+    return (out, q) if out is not None else q
+
+
+def tft_vsn_pack(vsn, emb_vectors, emb_bias, dtype, device):
+    """Parameter blocks of dle_tft_vsn_fwd for a selection network over F continuous variables.  `vsn` maps the reference's names
+    (joint_grn.*, var_grns.N.*) to tensors; emb_vectors / emb_bias [F, 128] are the embedding of the variables in the network's
+    column order.  The first linear of every network acts on x_f a_f + b_f, so it is folded here, in float64, into
+    x_f (W a_f) + (W b_f + bias); so is the out_proj of the joint network."""
+    H = TFT_HIDDEN
+    d = {k: v.detach().double().cpu() for k, v in vsn.items()}
+    a, b = emb_vectors.detach().double().cpu(), emb_bias.detach().double().cpu()
+    F = a.shape[0]
+    if not 1 <= F <= TFT_MAX_VARS or tuple(a.shape) != (F, H) or tuple(b.shape) != (F, H):
+        raise ValueError("tft_vsn_pack: 1 to 8 variables with [F, 128] embeddings (got %s)" % (list(a.shape),))
+    wa = d["joint_grn.lin_a.weight"].reshape(H, F, H)
+    ju = torch.einsum("nfh,fh->fn", wa, a)
+    jv = torch.einsum("nfh,fh->n", wa, b) + d["joint_grn.lin_a.bias"]
+    wo = d["joint_grn.out_proj.weight"].reshape(F, F, H)                      # [f_out, f_in, h]
+    jo = torch.zeros(F, 8, dtype=torch.float64)
+    jo[:, :F] = torch.einsum("ofh,fh->fo", wo, a)
+    jov = torch.zeros(8, dtype=torch.float64)
+    jov[:F] = torch.einsum("ofh,fh->o", wo, b) + d["joint_grn.out_proj.bias"]
+    wg = torch.zeros(32, H, dtype=torch.float64)
+    bg = torch.zeros(32, dtype=torch.float64)
+    wg[:F], wg[8:8 + F] = d["joint_grn.glu.lin.weight"][:F], d["joint_grn.glu.lin.weight"][F:]
+    bg[:F], bg[8:8 + F] = d["joint_grn.glu.lin.bias"][:F], d["joint_grn.glu.lin.bias"][F:]
+    gam, bet = torch.ones(8, dtype=torch.float64), torch.zeros(8, dtype=torch.float64)
+    if F > 1:
+        gam[:F], bet[:F] = d["joint_grn.layer_norm.ln.weight"], d["joint_grn.layer_norm.ln.bias"]
+    has_ctx = "joint_grn.lin_c.weight" in d
+    w16 = [d["joint_grn.lin_c.weight"] if has_ctx else torch.zeros(H, H, dtype=torch.float64), d["joint_grn.lin_i.weight"], wg]
+    p32 = [ju, jv, d["joint_grn.lin_i.bias"], bg, jo, jov, gam, bet]
+    for f in range(F):
+        g = "var_grns.%d." % f
+        w = d[g + "lin_a.weight"]
+        p32 += [w @ a[f], w @ b[f] + d[g + "lin_a.bias"], a[f], b[f], d[g + "lin_i.bias"], d[g + "glu.lin.bias"],
+                d[g + "layer_norm.ln.weight"], d[g + "layer_norm.ln.bias"]]
+        w16 += [d[g + "lin_i.weight"], d[g + "glu.lin.weight"]]
+    w16 = torch.cat([t.reshape(-1) for t in w16]).to(device=device, dtype=dtype)
+    p32 = torch.cat([t.reshape(-1) for t in p32]).to(device=device, dtype=torch.float32)
+    assert w16.numel() == 2 * H * H + 32 * H + F * 3 * H * H and p32.numel() == F * H + 2 * H + 32 + F * 8 + 24 + F * 9 * H
+    return {"w16": w16, "p32": p32, "F": F, "has_ctx": has_ctx}
+
+
+def tft_vsn_fwd(groups, p, dtype, steps, t0=0, ctx=None, out=None, out_t0=0, want_weights=False, eps=1e-3):
+    """Embedding + variable selection in one launch.  groups: up to three fp32 tensors [B, T, n_g] (contiguous) whose columns,
+    in order, are the F variables of the pack p; rows are steps t0 .. t0 + steps - 1 of every batch element; ctx [B, 128] or None.
+    out: [B, out_T, 128] (allocated as [B, steps, 128] when None), written at steps out_t0 .. out_t0 + steps - 1.
+    Returns out or (out, weights [B, steps, F] fp32)."""
+    name = "tft_vsn_fwd"
+    groups = [g for g in groups if g is not None]
+    C.require_cuda(*groups, ctx, out)
+    if not 1 <= len(groups) <= 3:
+        raise ValueError("%s: one to three variable groups" % name)
+    B, T = groups[0].shape[0], groups[0].shape[1]
+    for g in groups:
+        if g.dtype != torch.float32 or g.dim() != 3 or g.shape[0] != B or g.shape[1] != T or not g.is_contiguous():
+            raise ValueError("%s: every group must be a contiguous fp32 [B, T, n] tensor of one B and T" % name)
+    if sum(g.shape[2] for g in groups) != p["F"]:
+        raise ValueError("%s: %d columns for a network of %d variables" % (name, sum(g.shape[2] for g in groups), p["F"]))
+    if dtype not in _FP16 or p["w16"].dtype != dtype:
+        raise ValueError("%s: the pack is %s, the call %s" % (name, p["w16"].dtype, dtype))
+    steps, t0, out_t0 = int(steps), int(t0), int(out_t0)
+    if steps < 1 or t0 < 0 or t0 + steps > T:
+        raise ValueError("%s: steps %d .. %d of %d" % (name, t0, t0 + steps, T))
+    if (ctx is not None) != p["has_ctx"]:
+        raise ValueError("%s: the context and the network's lin_c go together" % name)
+    if ctx is not None:
+        _tft_rows16(name, ctx, "ctx")
+        if ctx.dtype != dtype or ctx.shape[0] != B:
+            raise ValueError("%s: ctx must be [B, 128] of the operand type" % name)
+    if out is None:
+        out = torch.empty((B, steps, TFT_HIDDEN), dtype=dtype, device=groups[0].device)
+    if out.dtype != dtype or out.dim() != 3 or out.shape[0] != B or out.shape[2] != TFT_HIDDEN or not out.is_contiguous() or \
+            out_t0 < 0 or out_t0 + steps > out.shape[1]:
+        raise ValueError("%s: out must be a contiguous [B, >= out_t0 + steps, 128] tensor of the operand type" % name)
+    weights = torch.empty((B, steps, p["F"]), dtype=torch.float32, device=out.device) if want_weights else None
+    seg = []
+    for i in range(3):
+        g = groups[i] if i < len(groups) else None
+        seg += [C.ptr(g), g.shape[2] if g is not None else 0, g.shape[2] if g is not None else 0]
+    C.annotate(flops=2.0 * B * steps * TFT_HIDDEN * TFT_HIDDEN * (2 + 3 * p["F"]), tag="tft_vsn %dx%d F%d" % (B, steps, p["F"]))
+    C.call("dle_tft_vsn_fwd", *seg, steps, T, t0, C.ptr(ctx), (ctx.stride(0) if B > 1 else TFT_HIDDEN) if ctx is not None else 0,
+           C.ptr(p["w16"]), C.ptr(p["p32"]), C.ptr(out), TFT_HIDDEN, out.shape[1], out_t0, C.ptr(weights), B * steps, TFT_HIDDEN,
+           float(eps), C.dt(dtype), C.stream())
+    return (out, weights) if want_weights else out
+
+
+def tft_lstm_fwd(xproj, whh, h0, c0, out=None, want_out=True):
+    """A whole LSTM layer in one launch.  xproj [B, T, 512] fp32 = W_ih x + b_ih + b_hh (any batch / step strides that are
+    multiples of 4, unit inner stride), whh [512, 128] 16-bit, h0 [B, 128] 16-bit, c0 [B, 128] fp32 or 16-bit.  out [B, T, 128]
+    (a step-slice of a larger contiguous tensor is fine).  Returns out, hn (16-bit), cn (fp32)."""
+    name = "tft_lstm_fwd"
+    C.require_cuda(xproj, whh, h0, c0, out)
+    if xproj.dtype != torch.float32 or xproj.dim() != 3 or xproj.shape[2] != 4 * TFT_HIDDEN or xproj.stride(2) != 1:
+        raise ValueError("%s: xproj must be fp32 [B, T, 512] with unit inner stride" % name)
+    B, T = xproj.shape[0], xproj.shape[1]
+    dtype = whh.dtype
+    if dtype not in _FP16:
+        raise ValueError("%s: 16-bit weights only" % name)
+    _tft_w16(name, whh, (4 * TFT_HIDDEN, TFT_HIDDEN), dtype, "whh")
+    _tft_w16(name, h0, (B, TFT_HIDDEN), dtype, "h0")
+    if c0.dtype not in (torch.float32, dtype) or tuple(c0.shape) != (B, TFT_HIDDEN) or not c0.is_contiguous():
+        raise ValueError("%s: c0 must be a contiguous [B, 128] tensor, fp32 or of the operand type" % name)
+    if T < 1 or B < 1:
+        raise ValueError("%s: empty batch or sequence" % name)
+    if want_out:
+        if out is None:
+            out = torch.empty((B, T, TFT_HIDDEN), dtype=dtype, device=xproj.device)
+        if out.dtype != dtype or tuple(out.shape) != (B, T, TFT_HIDDEN) or out.stride(2) != 1:
+            raise ValueError("%s: out must be [B, T, 128] of the operand type with unit inner stride" % name)
+    else:
+        out = None
+    hn = torch.empty((B, TFT_HIDDEN), dtype=dtype, device=xproj.device)
+    cn = torch.empty((B, TFT_HIDDEN), dtype=torch.float32, device=xproj.device)
+    C.annotate(flops=2.0 * B * T * 4 * TFT_HIDDEN * TFT_HIDDEN, tag="tft_lstm %dx%d" % (B, T))
+    C.call("dle_tft_lstm_fwd", C.ptr(xproj), xproj.stride(0) if B > 1 else T * xproj.stride(1), xproj.stride(1) if T > 1 else 4 * TFT_HIDDEN,
+           C.ptr(whh), C.ptr(h0), C.ptr(c0), C.dt(c0), C.ptr(out),
+           (out.stride(0) if B > 1 else T * out.stride(1)) if out is not None else 0,
+           (out.stride(1) if T > 1 else TFT_HIDDEN) if out is not None else 0, C.ptr(hn), C.ptr(cn), B, T, TFT_HIDDEN, C.dt(dtype), C.stream())
+    return out, hn, cn
+
+
+def tft_attention_fwd(qkv, wo, B, T, encoder_length, heads=4, want_probs=False):
+    """Interpretable multi-head attention for positions encoder_length .. T - 1: qkv [B * T, 288] 16-bit (q | k | shared v),
+    wo [128, 32].  Returns out [B, T - encoder_length, 128], or (out, mean probabilities [B, T - encoder_length, T] fp32)."""
+    name = "tft_attention_fwd"
+    C.require_cuda(qkv, wo)
+    B, T, enc, heads = int(B), int(T), int(encoder_length), int(heads)
+    if heads != 4:
+        raise ValueError("%s: built for 4 heads of 32 (got %d heads)" % (name, heads))
+    if qkv.dtype not in _FP16 or qkv.dim() != 2 or qkv.shape[1] != 288 or qkv.stride(1) != 1 or qkv.stride(0) % 8 or qkv.shape[0] != B * T:
+        raise ValueError("%s: qkv must be 16-bit [B * T, 288] with unit inner stride and a row pitch that is a multiple of 8" % name)
+    _tft_w16(name, wo, (TFT_HIDDEN, 32), qkv.dtype, "wo")
+    if not (2 <= T <= 192) or not (1 <= enc < T) or B < 1:
+        raise ValueError("%s: needs 2 <= T <= 192 and 1 <= encoder_length < T (got T %d, encoder_length %d)" % (name, T, enc))
+    out = torch.empty((B, T - enc, TFT_HIDDEN), dtype=qkv.dtype, device=qkv.device)
+    probs = torch.empty((B, T - enc, T), dtype=torch.float32, device=qkv.device) if want_probs else None
+    C.annotate(flops=2.0 * B * (T - enc) * T * 32 * 5, tag="tft_attn %dx%d/%d" % (B, T, enc))
+    C.call("dle_tft_attention_fwd", C.ptr(qkv), qkv.stride(0) if B * T > 1 else 288, C.ptr(wo), C.ptr(out), C.ptr(probs), B, T, enc, heads, 32,
+           C.dt(qkv), C.stream())
+    return (out, probs) if want_probs else out

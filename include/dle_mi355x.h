@@ -1124,6 +1124,49 @@ int dle_rows_gather_scale(const void* src, const int32_t* src_idx, void* dst, co
 int dle_row_nll(const float* logits, int64_t ld, const int32_t* target, const int32_t* pos, float* nll, int64_t rows,
                 int n_classes, int64_t n_out, int accumulate, hipStream_t stream);
 
+/* ---- Temporal Fusion Transformer inference (csrc/tft.hip; reference PyTorch/Forecasting/TFT/modeling.py) ---------------------
+ * Hidden size 128 only; 16-bit tensors (DLE_F16 / DLE_BF16) 16-byte aligned with pitches that are multiples of 8, weights
+ * row-major [out][in] as nn.Linear keeps them, biases / LayerNorm parameters / quantile weights fp32, accumulation fp32.
+ * Anything outside an envelope is -1 and a message, nothing launched.
+ *
+ * dle_tft_grn_fwd: GRN.forward (modeling.py:48-77) on 32 rows per workgroup, one launch:
+ *     h = ELU(wa x + ba [+ wc ctx[row / rows_per_ctx]]);  g = wi round16(h) + bi;  (a | b) = wg round16(g) + bg;
+ *     out = LayerNorm(a * sigmoid(b) + x; gamma, beta, eps)
+ *   x_index (int32 or NULL): row r of x is x[x_index[r]] (the static embedding gather, :169); an index outside [0, n_x_rows)
+ *   reads a zero row.  Gate mode, wa == NULL (wi, wc, ctx, ba, bi NULL too): the GLU is applied to x itself and the residual is
+ *   `res`, row r at res + r * ldr, or at res + (r / res_rows_per_batch) * res_batch_stride + (r % res_rows_per_batch) * ldr when
+ *   res_rows_per_batch > 0 -- input_gate / attention_gate / decoder_gate with their LayerNorms (:403-405, 418-420, 426-428).
+ *   Tail, qout != NULL: qout[r, q] = bq[q] + sum_n wq[q, n] out[r, n] on the unrounded LayerNorm output, 1 <= nq <= 8
+ *   (quantile_proj, :430); out may then be NULL.
+ * dle_tft_vsn_fwd: the embedding of continuous variables and VariableSelectionNetwork.forward (:162-189, 286-303) in one launch.
+ *   Row r = (b, t) of the launch reads the F = n0 + n1 + n2 raw values x_s[(b * src_steps + src_t0 + t) * ld_s + j] (fp32, up to
+ *   three column groups) and writes out[(b * out_steps + out_t0 + t) * ldo]; ctx [batch, ldc] or NULL; weights [rows, F] fp32 or
+ *   NULL.  w16 / p32 are the packed parameter blocks whose layout csrc/tft.hip states (functional.tft_vsn_pack builds them; the
+ *   first linear of every network is folded over the rank-1 embedding there).  1 <= F <= 8; with F == 1 the joint LayerNorm is
+ *   the Identity of MaybeLayerNorm and the weight is exactly 1.
+ * dle_tft_lstm_fwd: nn.LSTM(128, 128) over T steps (:368-370, 395-397), gates i, f, g, o: xproj fp32 = W_ih x + b_ih + b_hh for
+ *   every step, row (b, t) at xproj + b * xp_batch_stride + t * xp_step_stride; whh [512][128]; h0 [B, 128]; c0 [B, 128] fp32 or
+ *   the operand type (c0_dtype); out (16-bit, may be NULL) row (b, t) at out + b * out_batch_stride + t * out_step_stride; hn
+ *   [B, 128] 16-bit and cn [B, 128] fp32 (either may be NULL).  One workgroup per 32 batch rows, no wait between workgroups.
+ * dle_tft_attention_fwd: InterpretableMultiHeadAttention.forward behind qkv_linears for positions encoder_length .. T - 1 only
+ *   (:337-360, 414): qkv [B * T, ld >= 288] = (q of 4 heads | k of 4 heads | shared v), causal mask by index, mean of the heads'
+ *   probabilities times V, out_proj wo [128][32] -> out [B, T - encoder_length, 128]; probs (fp32 [B, T - encoder_length, T] or
+ *   NULL) receives the mean probabilities, zeros behind the mask.  4 heads of 32, 2 <= T <= 192, 1 <= encoder_length < T. */
+int dle_tft_grn_fwd(const void* x, int64_t ldx, const int32_t* x_index, int64_t n_x_rows, const void* ctx, int64_t ldc,
+                    int64_t rows_per_ctx, const void* res, int64_t ldr, int64_t res_rows_per_batch, int64_t res_batch_stride,
+                    const void* wa, const float* ba, const void* wc, const void* wi, const float* bi, const void* wg,
+                    const float* bg, const float* gamma, const float* beta, float eps, void* out, int64_t ldo, const float* wq,
+                    const float* bq, float* qout, int nq, int64_t rows, int hidden, int dtype, hipStream_t stream);
+int dle_tft_vsn_fwd(const float* x0, int64_t ld0, int n0, const float* x1, int64_t ld1, int n1, const float* x2, int64_t ld2, int n2,
+                    int64_t rows_per_batch, int64_t src_steps, int64_t src_t0, const void* ctx, int64_t ldc, const void* w16,
+                    const float* p32, void* out, int64_t ldo, int64_t out_steps, int64_t out_t0, float* weights, int64_t rows,
+                    int hidden, float eps, int dtype, hipStream_t stream);
+int dle_tft_lstm_fwd(const float* xproj, int64_t xp_batch_stride, int64_t xp_step_stride, const void* whh, const void* h0,
+                     const void* c0, int c0_dtype, void* out, int64_t out_batch_stride, int64_t out_step_stride, void* hn, float* cn,
+                     int B, int T, int hidden, int dtype, hipStream_t stream);
+int dle_tft_attention_fwd(const void* qkv, int64_t ld, const void* wo, void* out, float* probs, int B, int T, int encoder_length,
+                          int heads, int d_head, int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
