@@ -31,7 +31,7 @@
 //
 // The other kernels are bound by launch latency, not by bandwidth (rows x a few hundred channels): they are written for exactness
 // of their contract, one rounding per output, fp32 arithmetic in a fixed order without contraction where a test compares bits.
-#include "gemm_tiles.h"
+#include "conv1d_family.h"
 #include <math.h>
 
 // every product and sum below is rounded on its own (no fused multiply-add unless written as one): the row kernels promise bits
@@ -46,17 +46,6 @@
 #define FP_RT 16           // rows per workgroup of the row kernels (embed, scalar_conv_add, expand)
 #define FP_UT 64           // frames per workgroup of unpack_mel
 
-// sequence b of a table: first row and length, clamped so that [start, start + len) lies inside [0, total) and len <= max_len
-__device__ __forceinline__ void fp_seq(const int32_t* cu, int b, int max_len, long long total, long long& start, int& len) {
-  long long s = cu[b];
-  long long l = (long long)cu[b + 1] - s;
-  s = s < 0 ? 0 : (s > total ? total : s);
-  l = l < 0 ? 0 : (l > max_len ? max_len : l);
-  if (s + l > total) l = total - s;
-  start = s;
-  len = (int)l;
-}
-
 struct FpConvArgs {
   const unsigned short* x;     // [total, C]
   const unsigned short* w;     // [Ko, ksize, C]
@@ -69,45 +58,6 @@ struct FpConvArgs {
   float slope;
 };
 
-template <int DT>
-__device__ __forceinline__ ushort8_t fp_act8(ushort8_t v, float slope) {
-  ushort8_t o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float f = Elem<DT>::to_f32(v[e]);
-    o[e] = f < 0.f ? Elem<DT>::from_f32(f * slope) : v[e];
-  }
-  return o;
-}
-
-// The staged tile of one chunk, in two halves so that the global loads of chunk i + 1 are in flight while chunk i is multiplied:
-// fp_stage_load reads rows [t0 - halo, t0 - halo + rows) x channels [c0, c0 + 64) of the sequence at xs (len rows) into registers
-// (thread = 8 channels of rows r0, r0 + 32, r0 + 64; zeros outside [0, len) and beyond C, the activation applied here, once),
-// fp_stage_store writes them to lds[row][8 piece].
-template <int DT>
-__device__ __forceinline__ void fp_stage_load(ushort8_t* v, const unsigned short* xs, int len, int C, int t0, int halo, int rows,
-                                              int c0, float slope) {
-  const int cc = threadIdx.x & 7, r0 = threadIdx.x >> 3;
-  const int c = c0 + cc * 8;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int r = r0 + 32 * i, t = t0 - halo + r;
-    v[i] = ushort8_t{0, 0, 0, 0, 0, 0, 0, 0};
-    if (r < rows && t >= 0 && t < len && c < C) {
-      v[i] = *(const ushort8_t*)(xs + (long long)t * C + c);
-      if (slope != 1.f) v[i] = fp_act8<DT>(v[i], slope);
-    }
-  }
-}
-__device__ __forceinline__ void fp_stage_store(unsigned short* lds, const ushort8_t* v, int rows) {
-  const int cc = threadIdx.x & 7, r0 = threadIdx.x >> 3;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int r = r0 + 32 * i;
-    if (r < rows) *(ushort8_t*)(lds + r * FP_PITCH + cc * 8) = v[i];
-  }
-}
-
 // K3: ksize <= 3 (every convolution of FastPitch): the weight fragments of ALL taps of a chunk are held in registers and those of
 // the next chunk are loaded while this one is multiplied.  Otherwise (ksize 5 .. 11) one tap is loaded ahead, as hfg_conv1d_kernel
 // does.  Both walk taps, 16-channel steps and sub-tiles in the same order, so the accumulator sees the same sequence of MFMAs.
@@ -118,7 +68,7 @@ __global__ __launch_bounds__(256) void fp_conv1d_packed_kernel(FpConvArgs p) {
   const int b = blockIdx.x / p.ttiles, t0 = (blockIdx.x - b * p.ttiles) * FP_TT;
   long long start;
   int len;
-  fp_seq(p.cu, b, p.max_len, p.total, start, len);
+  c1d_seq(p.cu, b, p.total, start, len, p.max_len);
   if (t0 >= len) return;                                             // workgroup-uniform: before any barrier or LDS write
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 31, fh = lane >> 5;
@@ -130,7 +80,6 @@ __global__ __launch_bounds__(256) void fp_conv1d_packed_kernel(FpConvArgs p) {
   const unsigned short* xs = p.x + start * p.C;
   const unsigned short* wk0 = p.w + (long long)(ko_ok ? ko : 0) * p.ksize * p.C;
   const int rows = FP_TT + 2 * p.halo;
-  const ushort8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
 
   float16_t acc[NT];
 #pragma unroll
@@ -138,20 +87,7 @@ __global__ __launch_bounds__(256) void fp_conv1d_packed_kernel(FpConvArgs p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[nt][i] = 0.f;
 
-  // A fragments of one tap of the chunk at c0: lane = ko, channels c0 + 16 ks + 8 fh + e; zero beyond C and for the rows beyond Ko,
-  // where no address is formed and no load issued; the k-steps beyond the chunk (wave-uniform) are neither loaded nor multiplied
-  auto load_tap = [&](int c0, int tap, ushort8_t* f) {
-    const int cw = p.C - c0 < FP_CC ? p.C - c0 : FP_CC;
-    const int nks = (cw + 15) >> 4;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      f[ks] = zero;
-      if (ks < nks) {
-        const int c = c0 + ks * 16 + fh * 8;
-        if (ko_ok && c < p.C) f[ks] = *(const ushort8_t*)(wk0 + (long long)tap * p.C + c);
-      }
-    }
-  };
+  auto load_tap = [&](int c0, int tap, ushort8_t* f) { c1d_load_tap(f, wk0, tap, p.C, c0, fh, ko_ok); };
   auto load_taps = [&](int c0, ushort8_t (*f)[4]) {
 #pragma unroll
     for (int tap = 0; tap < WT; ++tap)
@@ -174,16 +110,16 @@ __global__ __launch_bounds__(256) void fp_conv1d_packed_kernel(FpConvArgs p) {
   };
 
   ushort8_t sv[3], wcur[WT][4], wnxt[WT][4];
-  fp_stage_load<DT>(sv, xs, len, p.C, t0, p.halo, rows, 0, p.slope);
+  c1d_stage_load<DT>(sv, xs, len, p.C, t0 - p.halo, rows, 0, p.slope);
   if (K3 && wave_on) load_taps(0, wcur);
   for (int c0 = 0; c0 < p.C; c0 += FP_CC) {
     const int cw = p.C - c0 < FP_CC ? p.C - c0 : FP_CC;
     const int nks = (cw + 15) >> 4;
     const bool more = c0 + FP_CC < p.C;
     if (c0) __syncthreads();                                          // every wave is done with the previous chunk's tile
-    fp_stage_store(lds, sv, rows);
+    c1d_stage_store<3, FP_PITCH>(lds, sv, rows);
     if (more) {                                                       // the next chunk's operands: in flight during this chunk's MFMAs
-      fp_stage_load<DT>(sv, xs, len, p.C, t0, p.halo, rows, c0 + FP_CC, p.slope);
+      c1d_stage_load<DT>(sv, xs, len, p.C, t0 - p.halo, rows, c0 + FP_CC, p.slope);
       if (K3 && wave_on) load_taps(c0 + FP_CC, wnxt);
     }
     __syncthreads();
@@ -218,33 +154,13 @@ __global__ __launch_bounds__(256) void fp_conv1d_packed_kernel(FpConvArgs p) {
     const int t = t0 + nt * 32 + fr;
     if (t >= len) continue;
     const long long row = (start + t) * p.Ko;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int k4 = kob + qd * 8 + fh * 4;
-      if (k4 >= p.Ko) continue;                                       // Ko % 8 == 0: a run of 4 is inside or outside whole
-      const float4_t bs = *(const float4_t*)(p.bias + k4);
-      ushort4_t a1 = {0, 0, 0, 0};
-      if (p.add1) a1 = *(const ushort4_t*)(p.add1 + row + k4);
-      ushort4_t o;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float v = acc[nt][qd * 4 + i] + bs[i];
-        if (p.add1) v += Elem<DT>::to_f32(a1[i]);
-        o[i] = Elem<DT>::from_f32(v);
-      }
-      *(ushort4_t*)(p.y + row + k4) = o;
-    }
+    c1d_epilogue_bias<DT>(acc[nt], p.bias, p.add1, nullptr, p.y, row, kob, fh, p.Ko, 1.f);
   }
-}
-
-static bool fp_overlap(const void* a, long long abytes, const void* b, long long bbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 // the (B, max_len, total) envelope every packed kernel shares with dle_attention_fwd_varlen
 #define FP_CHECK_TABLE(name, B, max_len, total)                                                                            \
-  DLE_CHECK_ARG((B) > 0 && (B) <= (1 << 20) && (total) > 0 && (total) < (1LL << 31), name ": bad batch / total rows");     \
+  DLE_CHECK_ARG(c1d_batch_ok(B, total, total) && (total) > 0, name ": bad batch / total rows");                            \
   DLE_CHECK_ARG((max_len) >= 1 && (max_len) <= FP_MAX_LEN, name ": 1 <= max_len <= 1024 (got %d)", (int)(max_len))
 
 extern "C" int dle_conv1d_packed_fwd(const void* x, const void* w, const float* bias, const void* add1, void* y,
@@ -256,13 +172,12 @@ extern "C" int dle_conv1d_packed_fwd(const void* x, const void* w, const float* 
   DLE_CHECK_ARG(Ko >= 8 && Ko <= 2048 && Ko % 8 == 0, "conv1d_packed_fwd: Ko must be a multiple of 8 in [8, 2048] (got %d)", Ko);
   DLE_CHECK_ARG(ksize >= 1 && ksize <= 11 && (ksize & 1), "conv1d_packed_fwd: ksize must be odd in [1, 11] (got %d)", ksize);
   DLE_CHECK_ARG(x && w && bias && y && cu_seqlens, "conv1d_packed_fwd: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)bias) | ((uintptr_t)add1) | ((uintptr_t)y)) & 15) &&
-                    !(((uintptr_t)cu_seqlens) & 3),
+  DLE_CHECK_ARG(c1d_aligned<16>(x, w, bias, add1, y) && c1d_aligned<4>(cu_seqlens),
                 "conv1d_packed_fwd: x, w, bias, add1 and y must be 16-byte aligned");
   const long long xbytes = (long long)total * C * 2, ybytes = (long long)total * Ko * 2;
-  DLE_CHECK_ARG(xbytes < 0xFFFFFFF0LL && ybytes < 0xFFFFFFF0LL, "conv1d_packed_fwd: each tensor must be smaller than 4 GiB");
-  DLE_CHECK_ARG(!fp_overlap(x, xbytes, y, ybytes), "conv1d_packed_fwd: y must not overlap x");
-  DLE_CHECK_ARG(!add1 || add1 == y || !fp_overlap(add1, ybytes, y, ybytes), "conv1d_packed_fwd: y overlaps add1 without being it");
+  DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "conv1d_packed_fwd: each tensor must be smaller than 4 GiB");
+  DLE_CHECK_ARG(!c1d_overlap(x, xbytes, y, ybytes), "conv1d_packed_fwd: y must not overlap x");
+  DLE_CHECK_ARG(c1d_addend_ok(add1, y, ybytes), "conv1d_packed_fwd: y overlaps add1 without being it");
   FpConvArgs p;
   p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.bias = bias; p.add1 = (const unsigned short*)add1;
   p.y = (unsigned short*)y; p.cu = cu_seqlens; p.total = total; p.max_len = max_len; p.C = C; p.Ko = Ko; p.ksize = ksize;
@@ -381,7 +296,7 @@ __global__ __launch_bounds__(256) void fp_embed_kernel(const int64_t* ids, const
   const int b = blockIdx.x / rtiles, p0 = (blockIdx.x - b * rtiles) * FP_RT;
   long long start;
   int len;
-  fp_seq(cu, b, max_len, total, start, len);
+  c1d_seq(cu, b, total, start, len, max_len);
   const int n = (len - p0 < FP_RT ? len - p0 : FP_RT) * D;              // <= 0: nothing to do
   for (int i = threadIdx.x; i < n; i += 256) {
     const int pr = p0 + i / D, c = i - (i / D) * D;
@@ -423,7 +338,7 @@ __global__ __launch_bounds__(256) void fp_scalar_conv_add_kernel(unsigned short*
   const int b = blockIdx.x / rtiles, p0 = (blockIdx.x - b * rtiles) * FP_RT;
   long long start;
   int len;
-  fp_seq(cu, b, max_len, total, start, len);
+  c1d_seq(cu, b, total, start, len, max_len);
   const int n = (len - p0 < FP_RT ? len - p0 : FP_RT) * D;
   const int halo = (ksize - 1) / 2;
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -467,7 +382,7 @@ __global__ __launch_bounds__(256) void fp_durations_kernel(const float* src, int
   for (int b = threadIdx.x; b < B; b += 256) {
     long long start;
     int len;
-    fp_seq(cu_in, b, max_len, total, start, len);
+    c1d_seq(cu_in, b, total, start, len, max_len);
     long long run = 0;
     for (int i = 0; i < len; ++i) {
       float d = src[start + i];
@@ -518,8 +433,8 @@ __global__ __launch_bounds__(256) void fp_expand_kernel(const unsigned short* en
   const int b = blockIdx.x / rtiles, p0 = (blockIdx.x - b * rtiles) * FP_RT;
   long long in0, out0;
   int in_len, out_len;
-  fp_seq(cu_in, b, max_in, total_in, in0, in_len);
-  fp_seq(cu_out, b, max_out, total_out, out0, out_len);
+  c1d_seq(cu_in, b, total_in, in0, in_len, max_in);
+  c1d_seq(cu_out, b, total_out, out0, out_len, max_out);
   if (p0 >= out_len) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int pr = p0 + wave; pr < p0 + FP_RT && pr < out_len; pr += 4) {
@@ -575,7 +490,7 @@ __global__ __launch_bounds__(256) void fp_unpack_mel_kernel(const unsigned short
   const int b = blockIdx.x / ttiles, t0 = (blockIdx.x - b * ttiles) * FP_UT;
   long long start;
   int len;
-  fp_seq(cu, b, t_pad, total, start, len);
+  c1d_seq(cu, b, total, start, len, t_pad);
   const int n = n_mel * FP_UT;
   for (int i = threadIdx.x; i < n; i += 256) {
     const int m = i / FP_UT, t = t0 + (i - m * FP_UT);

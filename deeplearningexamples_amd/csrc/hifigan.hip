@@ -22,7 +22,7 @@
 // dle_hfg_post_fwd.  conv_post + tanh (models.py:218-221): one output channel, so a dot product per time step, bound by its one
 // read of x: 256 time steps and their halo staged in LDS as above, the weights as fp32 in LDS (broadcast reads), one thread per
 // sample, sequential fp32 fma, tanhf.
-#include "gemm_tiles.h"
+#include "conv1d_family.h"
 
 #define HFG_CC 64          // channels per staged chunk
 #define HFG_PITCH 72       // LDS row pitch in elements
@@ -39,18 +39,6 @@ struct HfgArgs {
   float slope, alpha;
 };
 
-// 8 values of x -> a (leaky ReLU as an fp32 product rounded to the storage type; x >= 0, -0 and NaN pass unchanged)
-template <int DT>
-__device__ __forceinline__ ushort8_t hfg_lrelu8(ushort8_t v, float slope) {
-  ushort8_t o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float f = Elem<DT>::to_f32(v[e]);
-    o[e] = f < 0.f ? Elem<DT>::from_f32(f * slope) : v[e];
-  }
-  return o;
-}
-
 // rows [t0 - halo, t0 - halo + rows) x channels [c0, c0 + 8 npr) of image b -> lds[row][8 piece]; 256 threads
 template <int DT>
 __device__ __forceinline__ void hfg_stage(unsigned short* lds, const unsigned short* xb, int T, int C, int t0, int halo, int rows,
@@ -63,7 +51,7 @@ __device__ __forceinline__ void hfg_stage(unsigned short* lds, const unsigned sh
     ushort8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (t >= 0 && t < T && c < C) {
       v = *(const ushort8_t*)(xb + (long long)t * C + c);
-      if (slope != 1.f) v = hfg_lrelu8<DT>(v, slope);
+      if (slope != 1.f) v = c1d_act8<DT>(v, slope);
     }
     *(ushort8_t*)(lds + r * HFG_PITCH + cc * 8) = v;
   }
@@ -84,7 +72,6 @@ __global__ __launch_bounds__(256) void hfg_conv1d_kernel(HfgArgs p) {
   const unsigned short* xb = p.x + (long long)b * p.T * p.C;
   const unsigned short* wk0 = p.w + (long long)(ko_ok ? ko : 0) * p.ksize * p.C;   // row of ko; the channel offset is added per load
   const int rows = TT + 2 * p.halo;
-  const ushort8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
 
   float16_t acc[NT];
 #pragma unroll
@@ -99,19 +86,7 @@ __global__ __launch_bounds__(256) void hfg_conv1d_kernel(HfgArgs p) {
     hfg_stage<DT>(lds, xb, p.T, p.C, t0, p.halo, rows, c0, nks * 2, p.slope);
     __syncthreads();
     if (!wave_on) continue;
-    // A fragments of one tap: lane = ko, channels c0 + 16 ks + 8 fh + e; zero beyond C and for the rows beyond Ko, where no
-    // address is formed and no load issued (with C = 8 the upper half-step would otherwise read past the last row of w); the
-    // k-steps beyond the chunk (ks >= nks, wave-uniform) are not loaded either: their MFMAs are skipped below
-    auto load_tap = [&](int tap, ushort8_t* f) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        f[ks] = zero;
-        if (ks < nks) {
-          const int c = c0 + ks * 16 + fh * 8;
-          if (ko_ok && c < p.C) f[ks] = *(const ushort8_t*)(wk0 + (long long)tap * p.C + c);
-        }
-      }
-    };
+    auto load_tap = [&](int tap, ushort8_t* f) { c1d_load_tap(f, wk0, tap, p.C, c0, fh, ko_ok); };   // the next tap's A fragments
     ushort8_t nxt[4];
     load_tap(0, nxt);
     for (int tap = 0; tap < p.ksize; ++tap) {
@@ -140,30 +115,8 @@ __global__ __launch_bounds__(256) void hfg_conv1d_kernel(HfgArgs p) {
     const int t = t0 + (wt * NT + nt) * 32 + fr;
     if (t >= p.T) continue;
     const long long row = ((long long)b * p.T + t) * p.Ko;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int k4 = kob + qd * 8 + fh * 4;
-      if (k4 >= p.Ko) continue;                                       // Ko % 8 == 0: a run of 4 is inside or outside whole
-      const float4_t bs = *(const float4_t*)(p.bias + k4);
-      ushort4_t a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
-      if (p.add1) a1 = *(const ushort4_t*)(p.add1 + row + k4);
-      if (p.add2) a2 = *(const ushort4_t*)(p.add2 + row + k4);
-      ushort4_t o;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float v = acc[nt][qd * 4 + i] + bs[i];
-        if (p.add1) v += Elem<DT>::to_f32(a1[i]);
-        if (p.add2) v += Elem<DT>::to_f32(a2[i]);
-        o[i] = Elem<DT>::from_f32(v * p.alpha);
-      }
-      *(ushort4_t*)(p.y + row + k4) = o;
-    }
+    c1d_epilogue_bias<DT>(acc[nt], p.bias, p.add1, p.add2, p.y, row, kob, fh, p.Ko, p.alpha);
   }
-}
-
-static bool hfg_overlap(const void* a, long long abytes, const void* b, long long bbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 extern "C" int dle_conv1d_lrelu_fwd(const void* x, const void* w, const float* bias, const void* add1, const void* add2, void* y,
@@ -179,13 +132,13 @@ extern "C" int dle_conv1d_lrelu_fwd(const void* x, const void* w, const float* b
                 ksize, dilation);
   if (B == 0) return 0;
   DLE_CHECK_ARG(x && w && bias && y, "conv1d_lrelu_fwd: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)bias) | ((uintptr_t)add1) | ((uintptr_t)add2) | ((uintptr_t)y)) & 15),
+  DLE_CHECK_ARG(c1d_aligned<16>(x, w, bias, add1, add2, y),
                 "conv1d_lrelu_fwd: every operand must be 16-byte aligned");
   const long long xbytes = (long long)B * T * C * 2, ybytes = (long long)B * T * Ko * 2;
-  DLE_CHECK_ARG(xbytes < 0xFFFFFFF0LL && ybytes < 0xFFFFFFF0LL, "conv1d_lrelu_fwd: each tensor must be smaller than 4 GiB");
-  DLE_CHECK_ARG(!hfg_overlap(x, xbytes, y, ybytes), "conv1d_lrelu_fwd: y must not overlap x");
-  DLE_CHECK_ARG(!add1 || add1 == y || !hfg_overlap(add1, ybytes, y, ybytes), "conv1d_lrelu_fwd: y overlaps add1 without being it");
-  DLE_CHECK_ARG(!add2 || add2 == y || !hfg_overlap(add2, ybytes, y, ybytes), "conv1d_lrelu_fwd: y overlaps add2 without being it");
+  DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "conv1d_lrelu_fwd: each tensor must be smaller than 4 GiB");
+  DLE_CHECK_ARG(!c1d_overlap(x, xbytes, y, ybytes), "conv1d_lrelu_fwd: y must not overlap x");
+  DLE_CHECK_ARG(c1d_addend_ok(add1, y, ybytes), "conv1d_lrelu_fwd: y overlaps add1 without being it");
+  DLE_CHECK_ARG(c1d_addend_ok(add2, y, ybytes), "conv1d_lrelu_fwd: y overlaps add2 without being it");
   const int WK = Ko <= 32 ? 1 : Ko <= 64 ? 2 : 4;
   const int TT = (4 / WK) * 64;
   HfgArgs p;
@@ -244,10 +197,9 @@ extern "C" int dle_hfg_post_fwd(const void* x, const void* w, const float* bias,
   DLE_CHECK_ARG(ksize >= 1 && ksize <= HFG_POST_MAXK && (ksize & 1), "hfg_post_fwd: ksize must be odd in [1, 11] (got %d)", ksize);
   if (B == 0) return 0;
   DLE_CHECK_ARG(x && w && bias && audio, "hfg_post_fwd: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)audio)) & 15) && !(((uintptr_t)bias) & 3),
+  DLE_CHECK_ARG(c1d_aligned<16>(x, w, audio) && c1d_aligned<4>(bias),
                 "hfg_post_fwd: x, w and audio must be 16-byte aligned");
-  DLE_CHECK_ARG((long long)B * T * C * 2 < 0xFFFFFFF0LL && (long long)B * T * 4 < 0xFFFFFFF0LL,
-                "hfg_post_fwd: each tensor must be smaller than 4 GiB");
+  DLE_CHECK_ARG(c1d_under_4gib((long long)B * T * C * 2, (long long)B * T * 4), "hfg_post_fwd: each tensor must be smaller than 4 GiB");
   const int ttiles = (T + HFG_POST_TT - 1) / HFG_POST_TT;
   const long long gx = (long long)B * ttiles;
   DLE_CHECK_ARG(gx <= 0x7FFFFFFFLL, "hfg_post_fwd: too many time tiles");

@@ -34,7 +34,7 @@
 // LDS: 2 x rows x 144 B for the input image + 2 x 18,432 B for the slabs, rows = 127 stride + 1 + (ksize - 1) dilation:
 // 76,608 B at ksize 11 (two workgroups per CU), 81,792 B at ksize 29, 89,856 B at ksize 29 dilation 2, 118,368 B at stride 2
 // ksize 29 (one workgroup per CU); above 64 KiB the launch opts in through DLE_LAUNCH_LDS.
-#include "gemm_tiles.h"
+#include "conv1d_family.h"
 
 #define JS_TT 128          // output rows per time tile
 #define JS_KB 128          // output channels per workgroup
@@ -55,22 +55,6 @@ struct JsArgs {
   int B, C, Ko, ksize, rows, relu;
 };
 
-// sequence b of a table: first row and length, clamped so that [start, start + len) lies inside [0, total)
-__device__ __forceinline__ void js_seq(const int32_t* cu, int b, long long total, long long& start, long long& len) {
-  long long s = cu[b];
-  long long l = (long long)cu[b + 1] - s;
-  s = s < 0 ? 0 : (s > total ? total : s);
-  l = l < 0 ? 0 : l;
-  if (s + l > total) l = total - s;
-  start = s;
-  len = l;
-}
-// the out_len a sequence really has: what the table says, never more than its (clamped) input gives
-__device__ __forceinline__ long long js_out_len(long long in_len, long long out_len_tab, int stride) {
-  const long long m = in_len > 0 ? (in_len - 1) / stride + 1 : 0;
-  return out_len_tab < m ? out_len_tab : m;
-}
-
 template <int DT, int S, int D>
 __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
   // staged input rows at the largest ksize, and the 16-byte pieces of them per thread
@@ -83,6 +67,8 @@ __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
   unsigned short* wl = js_lds + 2 * ximg;                          // [2][128][72]
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // The search is written out here as in qn_tcs_kernel: through a shared function the stride-2 instantiation measured 0.5 - 1.5 %
+  // slower at one utterance (Conv1) in four runs, and 0.993 of the parent's time written out (profiles/conv1d_family_variants.md).
   // (sequence, tile) of this workgroup: every wavefront runs the same search on the same data
   long long fb = -1, ft = 0;
   {
@@ -93,9 +79,9 @@ __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
       long long n = 0;
       if (b < p.B) {
         long long si, li, so, lo;
-        js_seq(p.cu_in, b, p.total_in, si, li);
-        js_seq(p.cu_out, b, p.total_out, so, lo);
-        n = (js_out_len(li, lo, S) + JS_TT - 1) / JS_TT;
+        c1d_seq(p.cu_in, b, p.total_in, si, li);
+        c1d_seq(p.cu_out, b, p.total_out, so, lo);
+        n = (c1d_out_len(li, lo, S) + JS_TT - 1) / JS_TT;
       }
       long long inc = n;                                           // inclusive prefix over the 64 lanes
 #pragma unroll
@@ -116,11 +102,11 @@ __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
   }
   if (fb < 0) return;                                              // workgroup-uniform, before any barrier
   const int b = (int)fb;
-  const long long t0 = ft * JS_TT;                                 // first output row of the tile inside its sequence
+  const long long t0 = ft * JS_TT;                         // first output row of the tile inside its sequence
   long long in0, in_len, out0, out_len;
-  js_seq(p.cu_in, b, p.total_in, in0, in_len);
-  js_seq(p.cu_out, b, p.total_out, out0, out_len);
-  out_len = js_out_len(in_len, out_len, S);
+  c1d_seq(p.cu_in, b, p.total_in, in0, in_len);
+  c1d_seq(p.cu_out, b, p.total_out, out0, out_len);
+  out_len = c1d_out_len(in_len, out_len, S);
   const int live = (int)(out_len - t0 < JS_TT ? out_len - t0 : JS_TT);     // >= 1 by construction
 
   const int fr = lane & 31, fh = lane >> 5;
@@ -144,6 +130,8 @@ __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
   // staging: thread = 8 channels (cc) of rows r0, r0 + 32, ...
   const int cc = threadIdx.x & 7, r0 = threadIdx.x >> 3;
   ushort8_t xr[XI], wreg[WI];
+  // load_x / store_x are c1d_stage_load / c1d_stage_store (conv1d_family.h) written out: through the shared pair the dilation-2
+  // instantiation measured 1.5 - 3 % slower (Conv2 at 1 and 16 utterances) and stride 2 about 1 %.
   auto load_x = [&](int c0) {
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
@@ -221,37 +209,15 @@ __global__ __launch_bounds__(256) void js_conv1d_bn_kernel(JsArgs p) {
     const long long row = (out0 + t0 + t) * p.Ko;
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int k4 = kob + nb * 32 + qd * 8 + fh * 4;
-        const float4_t sc = *(const float4_t*)(p.scale + k4), sh = *(const float4_t*)(p.shift + k4);
-        ushort4_t rs = {0, 0, 0, 0};
-        if (p.res) rs = *(const ushort4_t*)(p.res + row + k4);
-        ushort4_t o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = __builtin_fmaf(sc[i], acc[nb][nt][qd * 4 + i], sh[i]);
-          if (p.res) v += Elem<DT>::to_f32(rs[i]);
-          if (p.relu) v = v > 0.f ? v : 0.f;
-          o[i] = Elem<DT>::from_f32(v);
-        }
-        *(ushort4_t*)(p.y + row + k4) = o;
-      }
+      c1d_epilogue_bn<DT>(acc[nb][nt], p.scale, p.shift, p.res, p.y, row, kob + nb * 32, fh, p.relu);
   }
-}
-
-static bool js_overlap(const void* a, long long abytes, const void* b, long long bbytes) {
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 template <int DT>
 static void js_launch(const JsArgs& p, dim3 grid, int lds, int stride, int dilation, hipStream_t stream) {
-  const dim3 block(256);
-  if (stride == 2) DLE_LAUNCH_LDS((js_conv1d_bn_kernel<DT, 2, 1>), grid, block, lds, stream, p);
-  else if (dilation == 2) DLE_LAUNCH_LDS((js_conv1d_bn_kernel<DT, 1, 2>), grid, block, lds, stream, p);
-  else DLE_LAUNCH_LDS((js_conv1d_bn_kernel<DT, 1, 1>), grid, block, lds, stream, p);
+#define JS_KERNEL(S, D) js_conv1d_bn_kernel<DT, S, D>               // DT: this function's
+  C1D_LAUNCH_SD(JS_KERNEL, stride, dilation, grid, dim3(256), lds, stream, p);
+#undef JS_KERNEL
 }
 
 extern "C" int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* residual,
@@ -259,8 +225,7 @@ extern "C" int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const floa
                                         int64_t total_out, int C, int Ko, int ksize, int stride, int dilation, int relu, int dtype,
                                         hipStream_t stream) {
   DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "conv1d_bn_packed_fwd: 16-bit activations and weights only");
-  DLE_CHECK_ARG(B >= 1 && B <= (1 << 20) && total_in >= 0 && total_in < (1LL << 31) && total_out >= 0 && total_out <= total_in,
-                "conv1d_bn_packed_fwd: bad batch / total rows");
+  DLE_CHECK_ARG(c1d_batch_ok(B, total_in, total_out), "conv1d_bn_packed_fwd: bad batch / total rows");
   DLE_CHECK_ARG(C >= 64 && C <= 1024 && C % 64 == 0, "conv1d_bn_packed_fwd: C must be a multiple of 64 in [64, 1024] (got %d)", C);
   DLE_CHECK_ARG(Ko >= 64 && Ko <= 1024 && Ko % 64 == 0, "conv1d_bn_packed_fwd: Ko must be a multiple of 64 in [64, 1024] (got %d)", Ko);
   DLE_CHECK_ARG(ksize >= 1 && ksize <= JS_MAXK && (ksize & 1), "conv1d_bn_packed_fwd: ksize must be odd in [1, 29] (got %d)", ksize);
@@ -268,14 +233,13 @@ extern "C" int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const floa
                 "conv1d_bn_packed_fwd: stride and dilation in {1, 2}, not both 2 (got %d, %d)", stride, dilation);
   if (total_out == 0) return 0;
   DLE_CHECK_ARG(x && w && scale && shift && y && cu_in && cu_out, "conv1d_bn_packed_fwd: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)scale) | ((uintptr_t)shift) | ((uintptr_t)residual) |
-                   ((uintptr_t)y)) & 15) && !((((uintptr_t)cu_in) | ((uintptr_t)cu_out)) & 3),
+  DLE_CHECK_ARG(c1d_aligned<16>(x, w, scale, shift, residual, y) && c1d_aligned<4>(cu_in, cu_out),
                 "conv1d_bn_packed_fwd: x, w, scale, shift, residual and y must be 16-byte aligned");
   const long long xbytes = (long long)total_in * C * 2, ybytes = (long long)total_out * Ko * 2;
   const long long wbytes = (long long)Ko * ksize * C * 2;
-  DLE_CHECK_ARG(xbytes < 0xFFFFFFF0LL && ybytes < 0xFFFFFFF0LL, "conv1d_bn_packed_fwd: each tensor must be smaller than 4 GiB");
-  DLE_CHECK_ARG(!js_overlap(x, xbytes, y, ybytes) && !js_overlap(residual, ybytes, y, ybytes) && !js_overlap(w, wbytes, y, ybytes) &&
-                    !js_overlap(scale, Ko * 4LL, y, ybytes) && !js_overlap(shift, Ko * 4LL, y, ybytes),
+  DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "conv1d_bn_packed_fwd: each tensor must be smaller than 4 GiB");
+  DLE_CHECK_ARG(!c1d_overlap(x, xbytes, y, ybytes) && !c1d_overlap(residual, ybytes, y, ybytes) && !c1d_overlap(w, wbytes, y, ybytes) &&
+                    !c1d_overlap(scale, Ko * 4LL, y, ybytes) && !c1d_overlap(shift, Ko * 4LL, y, ybytes),
                 "conv1d_bn_packed_fwd: y must not overlap x, w, scale, shift or residual");
   JsArgs p;
   p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.scale = scale; p.shift = shift;

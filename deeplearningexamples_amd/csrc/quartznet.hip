@@ -33,7 +33,7 @@
 //  time tiles) the grid is below the CU count either way, so a wider channel block would only lower the workgroup count.
 //
 // dle_qn_normalize_pack, dle_ctc_greedy_packed -- bound by launch latency; written for exactness of their contract.
-#include "gemm_tiles.h"
+#include "conv1d_family.h"
 #include <math.h>
 
 #define QN_TT 64           // output rows per time tile
@@ -41,17 +41,6 @@
 #define QN_CC 64           // input channels per staged chunk
 #define QN_DP 72           // pitch (elements) of the d tile: the 16 rows of a ds_read_b128 lane group cover the 64 banks once
 #define QN_RG 8            // output rows per depthwise thread; also the tap block
-
-// sequence b of a table: first row and length, clamped so that [start, start + len) lies inside [0, total)
-__device__ __forceinline__ void qn_seq(const int32_t* cu, int b, long long total, long long& start, long long& len) {
-  long long s = cu[b];
-  long long l = (long long)cu[b + 1] - s;
-  s = s < 0 ? 0 : (s > total ? total : s);
-  l = l < 0 ? 0 : l;
-  if (s + l > total) l = total - s;
-  start = s;
-  len = l;
-}
 
 struct QnTcsArgs {
   const unsigned short* x;      // [total_in, C]
@@ -68,12 +57,6 @@ struct QnTcsArgs {
   int B, C, Ko, ksize, kp, rstage, rreal, relu;
 };
 
-// the out_len a sequence really has: what the table says, never more than its (clamped) input gives
-__device__ __forceinline__ long long qn_out_len(long long in_len, long long out_len_tab, int stride) {
-  const long long m = in_len > 0 ? (in_len - 1) / stride + 1 : 0;
-  return out_len_tab < m ? out_len_tab : m;
-}
-
 template <int DT, int S, int D, bool PF>
 __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short qn_lds[];
@@ -83,6 +66,8 @@ __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
   __shared__ long long s_where[2];                               // (sequence, tile) of this workgroup; sequence -1: none
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // The search is written out here as in js_conv1d_bn_kernel: through a shared function the prefetch form measured 1 - 2 % slower
+  // per unit and 8 - 9 % slower at dilation 2 (ksize 87), same registers but another scalar spilled (profiles/conv1d_family_variants.md).
   if (wave == 0) {
     const long long g = blockIdx.x;
     long long run = 0, fb = -1, ft = 0;
@@ -91,9 +76,9 @@ __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
       long long n = 0;
       if (b < p.B) {
         long long si, li, so, lo;
-        qn_seq(p.cu_in, b, p.total_in, si, li);
-        qn_seq(p.cu_out, b, p.total_out, so, lo);
-        n = (qn_out_len(li, lo, S) + QN_TT - 1) / QN_TT;
+        c1d_seq(p.cu_in, b, p.total_in, si, li);
+        c1d_seq(p.cu_out, b, p.total_out, so, lo);
+        n = (c1d_out_len(li, lo, S) + QN_TT - 1) / QN_TT;
       }
       long long inc = n;                                           // inclusive prefix over the 64 lanes
 #pragma unroll
@@ -118,9 +103,9 @@ __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
   const int b = (int)s_where[0];
   const long long t0 = s_where[1] * QN_TT;                         // first output row of the tile inside its sequence
   long long in0, in_len, out0, out_len;
-  qn_seq(p.cu_in, b, p.total_in, in0, in_len);
-  qn_seq(p.cu_out, b, p.total_out, out0, out_len);
-  out_len = qn_out_len(in_len, out_len, S);
+  c1d_seq(p.cu_in, b, p.total_in, in0, in_len);
+  c1d_seq(p.cu_out, b, p.total_out, out0, out_len);
+  out_len = c1d_out_len(in_len, out_len, S);
   const int live = (int)(out_len - t0 < QN_TT ? out_len - t0 : QN_TT);     // >= 1 by construction
   const int nts = live > 32 ? 2 : 1;
 
@@ -142,6 +127,8 @@ __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
   const int p0 = rg * QN_RG;
   const ushort8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
 
+  // The staging below stays private to this kernel: through c1d_stage_load / c1d_stage_store (conv1d_family.h) the prefetch form
+  // went from 2 to 28 - 45 scalar spills and from 251 to 255 VGPRs.
   // The staged operands of one chunk in two halves, so that the global loads of chunk i + 1 are in flight while chunk i is
   // computed: qn_load reads the input rows and the taps into registers (thread = 8 channels of rows r0, r0 + 32, ...; zeros outside
   // [0, len) of the own sequence and for the padding taps), qn_store writes them to LDS behind the barrier.
@@ -273,37 +260,15 @@ __global__ __launch_bounds__(256) void qn_tcs_kernel(QnTcsArgs p) {
     const long long row = (out0 + t0 + t) * p.Ko;
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int k4 = kob + nb * 32 + qd * 8 + fh * 4;
-        const float4_t sc = *(const float4_t*)(p.scale + k4), sh = *(const float4_t*)(p.shift + k4);
-        ushort4_t rs = {0, 0, 0, 0};
-        if (p.res) rs = *(const ushort4_t*)(p.res + row + k4);
-        ushort4_t o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = __builtin_fmaf(sc[i], acc[nb][nt][qd * 4 + i], sh[i]);
-          if (p.res) v += Elem<DT>::to_f32(rs[i]);
-          if (p.relu) v = v > 0.f ? v : 0.f;
-          o[i] = Elem<DT>::from_f32(v);
-        }
-        *(ushort4_t*)(p.y + row + k4) = o;
-      }
+      c1d_epilogue_bn<DT>(acc[nb][nt], p.scale, p.shift, p.res, p.y, row, kob + nb * 32, fh, p.relu);
   }
-}
-
-static bool qn_overlap(const void* a, long long abytes, const void* b, long long bbytes) {
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 template <int DT, bool PF>
 static void qn_tcs_launch(const QnTcsArgs& p, dim3 grid, int lds, int stride, int dilation, hipStream_t stream) {
-  const dim3 block(256);
-  if (stride == 2) DLE_LAUNCH_LDS((qn_tcs_kernel<DT, 2, 1, PF>), grid, block, lds, stream, p);
-  else if (dilation == 2) DLE_LAUNCH_LDS((qn_tcs_kernel<DT, 1, 2, PF>), grid, block, lds, stream, p);
-  else DLE_LAUNCH_LDS((qn_tcs_kernel<DT, 1, 1, PF>), grid, block, lds, stream, p);
+#define QN_KERNEL(S, D) qn_tcs_kernel<DT, S, D, PF>                 // DT, PF: this function's
+  C1D_LAUNCH_SD(QN_KERNEL, stride, dilation, grid, dim3(256), lds, stream, p);
+#undef QN_KERNEL
 }
 
 static std::atomic<int> qn_pf_mode{2};
@@ -318,8 +283,7 @@ extern "C" int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const vo
                                          int B, int64_t total_in, int64_t total_out, int C, int Ko, int ksize, int stride,
                                          int dilation, int relu, int dtype, hipStream_t stream) {
   DLE_CHECK_ARG(dtype == DLE_F16 || dtype == DLE_BF16, "tcs_conv1d_packed_fwd: 16-bit activations and weights only");
-  DLE_CHECK_ARG(B >= 1 && B <= (1 << 20) && total_in >= 0 && total_in < (1LL << 31) && total_out >= 0 && total_out <= total_in,
-                "tcs_conv1d_packed_fwd: bad batch / total rows");
+  DLE_CHECK_ARG(c1d_batch_ok(B, total_in, total_out), "tcs_conv1d_packed_fwd: bad batch / total rows");
   DLE_CHECK_ARG(C >= 64 && C <= 1024 && C % 64 == 0, "tcs_conv1d_packed_fwd: C must be a multiple of 64 in [64, 1024] (got %d)", C);
   DLE_CHECK_ARG(Ko >= 64 && Ko <= 1024 && Ko % 64 == 0, "tcs_conv1d_packed_fwd: Ko must be a multiple of 64 in [64, 1024] (got %d)", Ko);
   DLE_CHECK_ARG(ksize >= 3 && ksize <= 127 && (ksize & 1), "tcs_conv1d_packed_fwd: ksize must be odd in [3, 127] (got %d)", ksize);
@@ -327,14 +291,12 @@ extern "C" int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const vo
                 "tcs_conv1d_packed_fwd: stride and dilation in {1, 2}, not both 2 (got %d, %d)", stride, dilation);
   if (total_out == 0) return 0;
   DLE_CHECK_ARG(x && dw && pw && scale && shift && y && cu_in && cu_out, "tcs_conv1d_packed_fwd: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)x) | ((uintptr_t)dw) | ((uintptr_t)pw) | ((uintptr_t)scale) | ((uintptr_t)shift) |
-                   ((uintptr_t)residual) | ((uintptr_t)y) | ((uintptr_t)d_out)) & 15) &&
-                    !((((uintptr_t)cu_in) | ((uintptr_t)cu_out)) & 3),
+  DLE_CHECK_ARG(c1d_aligned<16>(x, dw, pw, scale, shift, residual, y, d_out) && c1d_aligned<4>(cu_in, cu_out),
                 "tcs_conv1d_packed_fwd: x, dw, pw, scale, shift, residual, y and d_out must be 16-byte aligned");
   const long long xbytes = (long long)total_in * C * 2, ybytes = (long long)total_out * Ko * 2, dbytes = (long long)total_out * C * 2;
-  DLE_CHECK_ARG(xbytes < 0xFFFFFFF0LL && ybytes < 0xFFFFFFF0LL, "tcs_conv1d_packed_fwd: each tensor must be smaller than 4 GiB");
-  DLE_CHECK_ARG(!qn_overlap(x, xbytes, y, ybytes) && !qn_overlap(residual, ybytes, y, ybytes) && !qn_overlap(d_out, dbytes, y, ybytes) &&
-                    !qn_overlap(d_out, dbytes, x, xbytes) && !qn_overlap(d_out, dbytes, residual, ybytes),
+  DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "tcs_conv1d_packed_fwd: each tensor must be smaller than 4 GiB");
+  DLE_CHECK_ARG(!c1d_overlap(x, xbytes, y, ybytes) && !c1d_overlap(residual, ybytes, y, ybytes) && !c1d_overlap(d_out, dbytes, y, ybytes) &&
+                    !c1d_overlap(d_out, dbytes, x, xbytes) && !c1d_overlap(d_out, dbytes, residual, ybytes),
                 "tcs_conv1d_packed_fwd: y and d_out must not overlap x, residual or each other");
   QnTcsArgs p;
   p.x = (const unsigned short*)x; p.dw = (const unsigned short*)dw; p.pw = (const unsigned short*)pw; p.scale = scale; p.shift = shift;
@@ -347,9 +309,9 @@ extern "C" int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const vo
   const long long gx = total_out / QN_TT + B;
   DLE_CHECK_ARG(gx <= 0x7FFFFFFFLL, "tcs_conv1d_packed_fwd: too many time tiles");
   const dim3 grid((unsigned)gx, (unsigned)((Ko + QN_KB - 1) / QN_KB));
-  // PF, the register prefetch of the next chunk behind LDS-only barriers: 255 - 256 VGPRs, ONE wavefront per SIMD, so one workgroup
+  // PF, the register prefetch of the next chunk behind LDS-only barriers: 237 - 251 VGPRs, ONE wavefront per SIMD, so one workgroup
   // per CU.  While the grid gives a CU at most one workgroup anyway, the kernel waits on its own loads and the prefetch pays; with
-  // more workgroups than CUs the plain form (170 - 188 VGPRs, two workgroups per CU, which cover each other's loads) is the faster
+  // more workgroups than CUs the plain form (144 - 158 VGPRs, two workgroups per CU, which cover each other's loads) is the faster
   // one.  Both forms compute the same bits; dle_tcs_prefetch_mode forces one of them (tests, A/B timing).
   const DleDeviceLimits* lim = dle_device_limits();
   const int mode = qn_pf_mode.load(std::memory_order_relaxed);
@@ -370,7 +332,7 @@ __global__ __launch_bounds__(256) void qn_normalize_pack_kernel(const float* x, 
   __shared__ float s_mean[8], s_den[8];
   const int b = blockIdx.x, f0 = blockIdx.y * 8;
   long long start, len;
-  qn_seq(cu, b, total, start, len);
+  c1d_seq(cu, b, total, start, len);
   if (lead > 0) {                                                   // workgroup-uniform
     const long long nz = len < lead ? len : lead;
     const ushort8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -416,7 +378,7 @@ extern "C" int dle_qn_normalize_pack_lead(const float* x, void* y, const int32_t
   DLE_CHECK_ARG(T_pad >= 1 && (long long)B * F * T_pad < (1LL << 31), "qn_normalize_pack: bad T_pad (%d)", T_pad);
   if (total == 0) return 0;
   DLE_CHECK_ARG(x && y && cu_seqlens, "qn_normalize_pack: null pointer");
-  DLE_CHECK_ARG(!(((uintptr_t)y) & 15) && !((((uintptr_t)x) | ((uintptr_t)cu_seqlens)) & 3), "qn_normalize_pack: y must be 16-byte aligned");
+  DLE_CHECK_ARG(c1d_aligned<16>(y) && c1d_aligned<4>(x, cu_seqlens), "qn_normalize_pack: y must be 16-byte aligned");
   const dim3 grid((unsigned)B, (unsigned)(F / 8)), block(256);
   if (dtype == DLE_F16)
     hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_F16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad, lead);
@@ -442,7 +404,7 @@ __global__ __launch_bounds__(256) void qn_ctc_greedy_kernel(const float* logits,
   __shared__ int s_cnt[4];
   const int b = blockIdx.x;
   long long start, len;
-  qn_seq(cu, b, total, start, len);
+  c1d_seq(cu, b, total, start, len);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int blank = n_classes - 1;
   for (long long r = wave; r < len; r += 4) {
@@ -494,12 +456,11 @@ __global__ __launch_bounds__(256) void qn_ctc_greedy_kernel(const float* logits,
 
 extern "C" int dle_ctc_greedy_packed(const float* logits, float* logp, int32_t* ids, int32_t* tokens, int32_t* n_tokens,
                                      const int32_t* cu_seqlens, int B, int64_t total, int n_classes, int ld, hipStream_t stream) {
-  DLE_CHECK_ARG(B >= 1 && B <= (1 << 20) && total >= 0 && total < (1LL << 31), "ctc_greedy_packed: bad batch / total rows");
+  DLE_CHECK_ARG(c1d_batch_ok(B, total, total), "ctc_greedy_packed: bad batch / total rows");
   DLE_CHECK_ARG(n_classes >= 2 && n_classes <= 4096 && ld >= n_classes && ld <= 65536,
                 "ctc_greedy_packed: 2 <= n_classes <= 4096 and n_classes <= ld (got %d, %d)", n_classes, ld);
   DLE_CHECK_ARG(n_tokens && cu_seqlens && (total == 0 || (logits && ids && tokens)), "ctc_greedy_packed: null pointer");
-  DLE_CHECK_ARG(!((((uintptr_t)logits) | ((uintptr_t)logp) | ((uintptr_t)ids) | ((uintptr_t)tokens) | ((uintptr_t)n_tokens) |
-                   ((uintptr_t)cu_seqlens)) & 3), "ctc_greedy_packed: misaligned operand");
+  DLE_CHECK_ARG(c1d_aligned<4>(logits, logp, ids, tokens, n_tokens, cu_seqlens), "ctc_greedy_packed: misaligned operand");
   hipLaunchKernelGGL(qn_ctc_greedy_kernel, dim3((unsigned)B), dim3(256), 0, stream, logits, logp, ids, tokens, n_tokens, cu_seqlens,
                      (long long)total, n_classes, ld);
   DLE_LAUNCH_CHECK();

@@ -1913,7 +1913,7 @@ def conv1d_lrelu_fwd(x, w, bias, dilation=1, slope=1.0, alpha=1.0, add1=None, ad
     [B, T, Ko] -> y [B, T, Ko].  slope = 1: no activation.  `out` may be add1 or add2 itself, never x.  Anything outside the
     kernel's envelope (include/dle_mi355x.h) raises ValueError."""
     C.require_cuda(x, w, bias, add1, add2, out)
-    if x.dtype not in (torch.float16, torch.bfloat16):
+    if x.dtype not in _FP16:
         raise ValueError("conv1d_lrelu_fwd: 16-bit activations and weights only (got %s)" % x.dtype)
     if x.dim() != 3 or w.dim() != 3 or not x.is_contiguous() or not w.is_contiguous() or w.dtype != x.dtype or w.shape[2] != x.shape[2]:
         raise ValueError("conv1d_lrelu_fwd: x must be contiguous [B,T,C] and w contiguous [Ko,ksize,C] of x's dtype")
@@ -1924,10 +1924,8 @@ def conv1d_lrelu_fwd(x, w, bias, dilation=1, slope=1.0, alpha=1.0, add1=None, ad
     for a in (add1, add2):
         if a is not None and (tuple(a.shape) != (b, t, ko) or a.dtype != x.dtype or not a.is_contiguous()):
             raise ValueError("conv1d_lrelu_fwd: an addend must be a contiguous [B,T,Ko] tensor of x's dtype")
-    if out is None:
-        out = torch.empty((b, t, ko), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (b, t, ko) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError("conv1d_lrelu_fwd: out must be a contiguous [B,T,Ko] tensor of x's dtype")
+    out = _out_tensor("conv1d_lrelu_fwd", out, (b, t, ko), x.dtype, x.device,
+                      text="out must be a contiguous [B,T,Ko] tensor of x's dtype")
     n_add = (add1 is not None) + (add2 is not None)
     C.annotate(flops=2.0 * b * t * ko * ks * c, tag="conv1d %dx%dx%d k%d ks%d d%d +%d" % (b, t, c, ko, ks, dilation, n_add),
                bytes=float(x.numel() + w.numel() + out.numel() * (1 + n_add)) * 2)
@@ -1940,46 +1938,45 @@ def hfg_post_fwd(x, w, bias, slope=0.01, out=None):
     """audio [B, T] fp32 = tanh(conv1d_same(leaky_relu(x, slope), w) + bias): the one-channel output convolution of the HiFi-GAN
     generator.  x [B, T, C] 16-bit (C % 8 == 0, C <= 64), w [ksize, C] of x's dtype, bias fp32 [1]."""
     C.require_cuda(x, w, bias, out)
-    if x.dtype not in (torch.float16, torch.bfloat16):
+    if x.dtype not in _FP16:
         raise ValueError("hfg_post_fwd: 16-bit activations and weights only (got %s)" % x.dtype)
     if x.dim() != 3 or w.dim() != 2 or not x.is_contiguous() or not w.is_contiguous() or w.dtype != x.dtype or w.shape[1] != x.shape[2]:
         raise ValueError("hfg_post_fwd: x must be contiguous [B,T,C] and w contiguous [ksize,C] of x's dtype")
     if bias.dtype != torch.float32 or bias.numel() != 1:
         raise ValueError("hfg_post_fwd: bias must be fp32 [1]")
     b, t, c = x.shape
-    if out is None:
-        out = torch.empty((b, t), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (b, t) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("hfg_post_fwd: out must be a contiguous fp32 [B,T] tensor")
+    out = _out_tensor("hfg_post_fwd", out, (b, t), torch.float32, x.device, text="out must be a contiguous fp32 [B,T] tensor")
     C.annotate(flops=2.0 * b * t * w.numel(), tag="hfg_post %dx%dx%d ks%d" % (b, t, c, w.shape[0]),
                bytes=float(x.numel()) * 2 + out.numel() * 4)
     C.call("dle_hfg_post_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(out), b, t, c, w.shape[0], float(slope), C.dt(x), C.stream())
     return out
 
 
-# ------------------------------------------------------------------ FastPitch on packed utterances (csrc/fastpitch.hip)
+# ------------------------------------------------------------------ packed utterances: the validators every wrapper below shares
 _FP16 = (torch.float16, torch.bfloat16)
 
 
-def _fp_table(name, cu, what="cu_seqlens"):
+def _cu_table(name, cu, what="cu_seqlens"):
     if cu is None or cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
         raise ValueError("%s: %s must be a contiguous int32 tensor [B + 1]" % (name, what))
     return cu.numel() - 1
 
 
-def _fp_f32(name, t, shape, what):
+def _f32_tensor(name, t, shape, what):
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError("%s: %s must be contiguous fp32 %s" % (name, what, list(shape)))
 
 
-def _fp_out(name, out, shape, dtype, device, what="out"):
+def _out_tensor(name, out, shape, dtype, device, what="out", text=None):
+    """`text`: the wrapper's own wording of the complaint (the HiFi-GAN wrappers name shapes by letter)."""
     if out is None:
         return torch.empty(shape, dtype=dtype, device=device)
     if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
-        raise ValueError("%s: %s must be a contiguous %s tensor %s" % (name, what, dtype, list(shape)))
+        raise ValueError("%s: %s" % (name, text or "%s must be a contiguous %s tensor %s" % (what, dtype, list(shape))))
     return out
 
 
+# ------------------------------------------------------------------ FastPitch on packed utterances (csrc/fastpitch.hip)
 def conv1d_packed_fwd(x, w, bias, cu_seqlens, max_len, slope=1.0, add1=None, out=None):
     """y = conv1d_same(act(x), w) + bias (+ add1) per SEQUENCE of a packed x [total, C] (16-bit, channels-last; sequence b owns rows
     cu_seqlens[b] .. cu_seqlens[b + 1] - 1; rows outside a row's own sequence read as zero), one launch, one rounding.  w [Ko, ksize, C]
@@ -1993,11 +1990,11 @@ def conv1d_packed_fwd(x, w, bias, cu_seqlens, max_len, slope=1.0, add1=None, out
         raise ValueError("%s: x must be contiguous [total,C] and w contiguous [Ko,ksize,C] of x's dtype" % name)
     total, c = x.shape
     ko, ks, _ = w.shape
-    b = _fp_table(name, cu_seqlens)
-    _fp_f32(name, bias, (ko,), "bias")
+    b = _cu_table(name, cu_seqlens)
+    _f32_tensor(name, bias, (ko,), "bias")
     if add1 is not None and (tuple(add1.shape) != (total, ko) or add1.dtype != x.dtype or not add1.is_contiguous()):
         raise ValueError("%s: add1 must be a contiguous [total,Ko] tensor of x's dtype" % name)
-    out = _fp_out(name, out, (total, ko), x.dtype, x.device)
+    out = _out_tensor(name, out, (total, ko), x.dtype, x.device)
     C.annotate(flops=2.0 * total * ko * ks * c, tag="conv1d_packed %dx%d k%d ks%d B%d" % (total, c, ko, ks, b),
                bytes=float(x.numel() + w.numel() + out.numel() * (2 if add1 is not None else 1)) * 2)
     C.call("dle_conv1d_packed_fwd", C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(add1), C.ptr(out), C.ptr(cu_seqlens), b, int(max_len),
@@ -2013,8 +2010,8 @@ def fp_relu_layernorm_fwd(x, gamma, beta, eps=1e-5, fc_w=None, fc_b=None, want_y
     if x.dtype not in _FP16 or x.dim() != 2 or not x.is_contiguous():
         raise ValueError("%s: x must be a contiguous 16-bit [rows, H] tensor" % name)
     rows, h = x.shape
-    _fp_f32(name, gamma, (h,), "gamma")
-    _fp_f32(name, beta, (h,), "beta")
+    _f32_tensor(name, gamma, (h,), "gamma")
+    _f32_tensor(name, beta, (h,), "beta")
     n_pred = 0
     if (fc_w is None) != (fc_b is None):
         raise ValueError("%s: fc_w and fc_b come together" % name)
@@ -2022,12 +2019,12 @@ def fp_relu_layernorm_fwd(x, gamma, beta, eps=1e-5, fc_w=None, fc_b=None, want_y
         if fc_w.dim() != 2:
             raise ValueError("%s: fc_w must be fp32 [n_pred, H]" % name)
         n_pred = fc_w.shape[0]
-        _fp_f32(name, fc_w, (n_pred, h), "fc_w")
-        _fp_f32(name, fc_b, (n_pred,), "fc_b")
+        _f32_tensor(name, fc_w, (n_pred, h), "fc_w")
+        _f32_tensor(name, fc_b, (n_pred,), "fc_b")
     if not want_y and not n_pred:
         raise ValueError("%s: neither y nor pred is wanted" % name)
-    y = _fp_out(name, out, (rows, h), x.dtype, x.device) if want_y else None
-    pred = _fp_out(name, pred_out, (rows, n_pred), torch.float32, x.device, "pred_out") if n_pred else None
+    y = _out_tensor(name, out, (rows, h), x.dtype, x.device) if want_y else None
+    pred = _out_tensor(name, pred_out, (rows, n_pred), torch.float32, x.device, "pred_out") if n_pred else None
     C.annotate(bytes=float(x.numel()) * 2 * (2 if want_y else 1), tag="relu_ln R%dxH%d p%d" % (rows, h, n_pred))
     C.call("dle_fp_relu_layernorm_fwd", C.ptr(x), C.ptr(y), C.ptr(gamma), C.ptr(beta), C.ptr(fc_w), C.ptr(fc_b), C.ptr(pred), rows, h,
            n_pred, float(eps), C.dt(x), C.stream())
@@ -2046,13 +2043,13 @@ def fp_embed(ids, word, pos, cu_seqlens, max_len, dtype, spk=None, out=None):
     if word.dim() != 2 or pos.dim() != 2:
         raise ValueError("%s: word and pos must be fp32 [rows, D]" % name)
     d = word.shape[1]
-    _fp_f32(name, word, (word.shape[0], d), "word")
-    _fp_f32(name, pos, (pos.shape[0], d), "pos")
+    _f32_tensor(name, word, (word.shape[0], d), "word")
+    _f32_tensor(name, pos, (pos.shape[0], d), "pos")
     if spk is not None:
-        _fp_f32(name, spk, (d,), "spk")
-    b = _fp_table(name, cu_seqlens)
+        _f32_tensor(name, spk, (d,), "spk")
+    b = _cu_table(name, cu_seqlens)
     total = ids.numel()
-    out = _fp_out(name, out, (total, d), dtype, ids.device)
+    out = _out_tensor(name, out, (total, d), dtype, ids.device)
     C.call("dle_fp_embed", C.ptr(ids), C.ptr(word), C.ptr(pos), C.ptr(spk), C.ptr(out), C.ptr(cu_seqlens), b, int(max_len), total,
            word.shape[0], pos.shape[0], d, C.dt(dtype), C.stream())
     return out
@@ -2066,12 +2063,12 @@ def fp_scalar_conv_add_(enc, v, w, bias, cu_seqlens, max_len):
     if enc.dtype not in _FP16 or enc.dim() != 2 or not enc.is_contiguous():
         raise ValueError("%s: enc must be a contiguous 16-bit [total, D] tensor" % name)
     total, d = enc.shape
-    _fp_f32(name, v, (total,), "v")
+    _f32_tensor(name, v, (total,), "v")
     if w.dim() != 2:
         raise ValueError("%s: w must be fp32 [D, ksize]" % name)
-    _fp_f32(name, w, (d, w.shape[1]), "w")
-    _fp_f32(name, bias, (d,), "bias")
-    b = _fp_table(name, cu_seqlens)
+    _f32_tensor(name, w, (d, w.shape[1]), "w")
+    _f32_tensor(name, bias, (d,), "bias")
+    b = _cu_table(name, cu_seqlens)
     C.annotate(bytes=float(enc.numel()) * 4, tag="scalar_conv R%dxD%d" % (total, d), replay=False)       # (adds into enc)
     C.call("dle_fp_scalar_conv_add", C.ptr(enc), C.ptr(v), C.ptr(w), C.ptr(bias), C.ptr(cu_seqlens), b, int(max_len), total, d,
            w.shape[1], C.dt(enc), C.stream())
@@ -2087,8 +2084,8 @@ def fp_durations(src, cu_seqlens, max_len, pace=1.0, max_duration=75.0, from_log
     if src.dim() != 1:
         raise ValueError("%s: src must be fp32 [total]" % name)
     total = src.numel()
-    _fp_f32(name, src, (total,), "src")
-    b = _fp_table(name, cu_seqlens)
+    _f32_tensor(name, src, (total,), "src")
+    b = _cu_table(name, cu_seqlens)
     if not (float(pace) > 0.0):
         raise ValueError("%s: pace must be positive (got %r)" % (name, pace))
     i32 = lambda n: torch.empty(n, dtype=torch.int32, device=src.device)
@@ -2109,14 +2106,14 @@ def fp_expand(enc, pos, reps, tok_start, cu_in, cu_out, max_in, max_out, total_o
     total_in, d = enc.shape
     if pos.dim() != 2:
         raise ValueError("%s: pos must be fp32 [n_pos, D]" % name)
-    _fp_f32(name, pos, (pos.shape[0], d), "pos")
+    _f32_tensor(name, pos, (pos.shape[0], d), "pos")
     for t, what in ((reps, "reps"), (tok_start, "tok_start")):
         if t.dtype != torch.int32 or tuple(t.shape) != (total_in,) or not t.is_contiguous():
             raise ValueError("%s: %s must be a contiguous int32 tensor [total_in]" % (name, what))
-    b = _fp_table(name, cu_in, "cu_in")
-    if _fp_table(name, cu_out, "cu_out") != b:
+    b = _cu_table(name, cu_in, "cu_in")
+    if _cu_table(name, cu_out, "cu_out") != b:
         raise ValueError("%s: cu_in and cu_out differ in length" % name)
-    out = _fp_out(name, out, (int(total_out), d), enc.dtype, enc.device)
+    out = _out_tensor(name, out, (int(total_out), d), enc.dtype, enc.device)
     C.call("dle_fp_expand", C.ptr(enc), C.ptr(pos), C.ptr(reps), C.ptr(tok_start), C.ptr(cu_in), C.ptr(cu_out), C.ptr(out), b,
            int(max_in), total_in, int(max_out), int(total_out), pos.shape[0], d, C.dt(enc), C.stream())
     return out
@@ -2129,9 +2126,9 @@ def fp_unpack_mel(x, bias, cu_seqlens, t_pad, out=None):
     if x.dtype not in _FP16 or x.dim() != 2 or not x.is_contiguous():
         raise ValueError("%s: x must be a contiguous 16-bit [total, n_mel] tensor" % name)
     total, n_mel = x.shape
-    _fp_f32(name, bias, (n_mel,), "bias")
-    b = _fp_table(name, cu_seqlens)
-    out = _fp_out(name, out, (b, n_mel, int(t_pad)), torch.float32, x.device)
+    _f32_tensor(name, bias, (n_mel,), "bias")
+    b = _cu_table(name, cu_seqlens)
+    out = _out_tensor(name, out, (b, n_mel, int(t_pad)), torch.float32, x.device)
     C.call("dle_fp_unpack_mel", C.ptr(x), C.ptr(bias), C.ptr(out), C.ptr(cu_seqlens), b, total, n_mel, int(t_pad), C.dt(x), C.stream())
     return out
 
@@ -2169,6 +2166,28 @@ def pad_ctc_decoder(weight, bias, dtype, rows=32):
     return wp.contiguous(), bp.contiguous()
 
 
+def _packed_conv_operands(name, x, ko, scale, shift, cu_in, cu_out, total_out, stride, residual, out):
+    """What tcs_conv1d_packed_fwd and conv1d_bn_packed_fwd share behind their weight checks: the two tables (stride 1: cu_out
+    defaults to cu_in and total_out to total_in), scale / shift / residual, and the output.  -> (B, cu_out, total_out, out)."""
+    b = _cu_table(name, cu_in, "cu_in")
+    if cu_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        cu_out = cu_in
+    elif _cu_table(name, cu_out, "cu_out") != b:
+        raise ValueError("%s: cu_in and cu_out must describe the same batch" % name)
+    if total_out is None:
+        if stride != 1:
+            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
+        total_out = x.shape[0]
+    total_out = int(total_out)
+    _f32_tensor(name, scale, (ko,), "scale")
+    _f32_tensor(name, shift, (ko,), "shift")
+    if residual is not None and (tuple(residual.shape) != (total_out, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
+        raise ValueError("%s: residual must be a contiguous [total_out,Ko] tensor of x's dtype" % name)
+    return b, cu_out, total_out, _out_tensor(name, out, (total_out, ko), x.dtype, x.device)
+
+
 def tcs_conv1d_packed_fwd(x, dw, pw, scale, shift, cu_in, cu_out=None, total_out=None, stride=1, dilation=1, residual=None,
                           relu=True, out=None, d_out=None):
     """One time-channel separable unit in one launch, per SEQUENCE of a packed x [total_in, C] (16-bit, channels-last):
@@ -2185,25 +2204,9 @@ def tcs_conv1d_packed_fwd(x, dw, pw, scale, shift, cu_in, cu_out=None, total_out
         raise ValueError("%s: x must be contiguous [total,C], dw contiguous [ksize,C] and pw contiguous [Ko,C] of x's dtype" % name)
     total_in, c = x.shape
     ks, ko = dw.shape[0], pw.shape[0]
-    b = _fp_table(name, cu_in, "cu_in")
-    if cu_out is None:
-        if stride != 1:
-            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
-        cu_out = cu_in
-    elif _fp_table(name, cu_out, "cu_out") != b:
-        raise ValueError("%s: cu_in and cu_out must describe the same batch" % name)
-    if total_out is None:
-        if stride != 1:
-            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
-        total_out = total_in
-    total_out = int(total_out)
-    _fp_f32(name, scale, (ko,), "scale")
-    _fp_f32(name, shift, (ko,), "shift")
-    if residual is not None and (tuple(residual.shape) != (total_out, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
-        raise ValueError("%s: residual must be a contiguous [total_out,Ko] tensor of x's dtype" % name)
-    out = _fp_out(name, out, (total_out, ko), x.dtype, x.device)
+    b, cu_out, total_out, out = _packed_conv_operands(name, x, ko, scale, shift, cu_in, cu_out, total_out, stride, residual, out)
     if d_out is not None:
-        d_out = _fp_out(name, d_out, (total_out, c), x.dtype, x.device, "d_out")
+        d_out = _out_tensor(name, d_out, (total_out, c), x.dtype, x.device, "d_out")
     C.annotate(flops=2.0 * total_out * c * (ko + ks), tag="tcs %dx%d k%d ks%d s%d d%d B%d" % (total_in, c, ko, ks, stride, dilation, b),
                bytes=float(x.numel() + dw.numel() + pw.numel() + out.numel() * (2 if residual is not None else 1)) * 2)
     C.call("dle_tcs_conv1d_packed_fwd", C.ptr(x), C.ptr(dw), C.ptr(pw), C.ptr(scale), C.ptr(shift), C.ptr(residual), C.ptr(out),
@@ -2218,41 +2221,37 @@ def tcs_prefetch_mode(mode=-1):
     return int(C.lib().dle_tcs_prefetch_mode(int(mode)))
 
 
-def qn_normalize_pack(x, cu_seqlens, total, dtype, out=None):
-    """Per-feature normalisation over each utterance's own frames (unbiased std + 1e-5), the mask, the transpose and the 16-bit cast
-    in one launch: x fp32 [B, F, T_pad] -> packed [total, F] of `dtype`."""
+def _qn_normalize_pack(name, x, cu_seqlens, total, dtype, lead, out):
+    """lead None: the entry without a lead (dle_qn_normalize_pack); otherwise dle_qn_normalize_pack_lead."""
     C.require_cuda(x, cu_seqlens, out)
-    name = "qn_normalize_pack"
     if dtype not in _FP16:
         raise ValueError("%s: 16-bit output only (got %s)" % (name, dtype))
     if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
         raise ValueError("%s: x must be a contiguous fp32 [B, F, T_pad] tensor" % name)
     b, f, t_pad = x.shape
-    if _fp_table(name, cu_seqlens) != b:
+    if _cu_table(name, cu_seqlens) != b:
         raise ValueError("%s: cu_seqlens must have B + 1 = %d entries" % (name, b + 1))
-    out = _fp_out(name, out, (int(total), f), dtype, x.device)
-    C.annotate(bytes=float(x.numel()) * 4 + float(out.numel()) * 2, tag="qn_normalize %dx%dx%d" % (b, f, t_pad))
-    C.call("dle_qn_normalize_pack", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(total), C.dt(dtype), C.stream())
+    out = _out_tensor(name, out, (int(total), f), dtype, x.device)
+    C.annotate(bytes=float(x.numel()) * 4 + float(out.numel()) * 2,
+               tag="qn_normalize %dx%dx%d" % (b, f, t_pad) + ("" if lead is None else " lead %d" % lead))
+    if lead is None:
+        C.call("dle_qn_normalize_pack", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(total), C.dt(dtype), C.stream())
+    else:
+        C.call("dle_qn_normalize_pack_lead", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(lead), int(total), C.dt(dtype),
+               C.stream())
     return out
+
+
+def qn_normalize_pack(x, cu_seqlens, total, dtype, out=None):
+    """Per-feature normalisation over each utterance's own frames (unbiased std + 1e-5), the mask, the transpose and the 16-bit cast
+    in one launch: x fp32 [B, F, T_pad] -> packed [total, F] of `dtype`."""
+    return _qn_normalize_pack("qn_normalize_pack", x, cu_seqlens, total, dtype, None, out)
 
 
 def qn_normalize_pack_lead(x, cu_seqlens, total, dtype, lead, out=None):
     """qn_normalize_pack with `lead` zero rows in front of every utterance (Jasper's --pad_leading, applied to the normalised
     features): cu_seqlens describes the OUTPUT rows, len_b + lead per sequence; the statistics run over the len_b real frames."""
-    C.require_cuda(x, cu_seqlens, out)
-    name = "qn_normalize_pack_lead"
-    if dtype not in _FP16:
-        raise ValueError("%s: 16-bit output only (got %s)" % (name, dtype))
-    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
-        raise ValueError("%s: x must be a contiguous fp32 [B, F, T_pad] tensor" % name)
-    b, f, t_pad = x.shape
-    if _fp_table(name, cu_seqlens) != b:
-        raise ValueError("%s: cu_seqlens must have B + 1 = %d entries" % (name, b + 1))
-    out = _fp_out(name, out, (int(total), f), dtype, x.device)
-    C.annotate(bytes=float(x.numel()) * 4 + float(out.numel()) * 2, tag="qn_normalize %dx%dx%d lead %d" % (b, f, t_pad, lead))
-    C.call("dle_qn_normalize_pack_lead", C.ptr(x), C.ptr(out), C.ptr(cu_seqlens), b, f, t_pad, int(lead), int(total), C.dt(dtype),
-           C.stream())
-    return out
+    return _qn_normalize_pack("qn_normalize_pack_lead", x, cu_seqlens, total, dtype, lead, out)
 
 
 def ctc_greedy_packed(logits, cu_seqlens, n_classes, want_logp=True, logp_out=None, ids_out=None, tokens_out=None, n_tokens_out=None):
@@ -2264,12 +2263,12 @@ def ctc_greedy_packed(logits, cu_seqlens, n_classes, want_logp=True, logp_out=No
     if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
         raise ValueError("%s: logits must be a contiguous fp32 [total, ld] tensor" % name)
     total, ld = logits.shape
-    b = _fp_table(name, cu_seqlens)
+    b = _cu_table(name, cu_seqlens)
     dev = logits.device
-    logp = _fp_out(name, logp_out, (total, int(n_classes)), torch.float32, dev, "logp") if (want_logp or logp_out is not None) else None
-    ids = _fp_out(name, ids_out, (total,), torch.int32, dev, "ids")
-    tokens = _fp_out(name, tokens_out, (total,), torch.int32, dev, "tokens")
-    n_tokens = _fp_out(name, n_tokens_out, (b,), torch.int32, dev, "n_tokens")
+    logp = _out_tensor(name, logp_out, (total, int(n_classes)), torch.float32, dev, "logp") if (want_logp or logp_out is not None) else None
+    ids = _out_tensor(name, ids_out, (total,), torch.int32, dev, "ids")
+    tokens = _out_tensor(name, tokens_out, (total,), torch.int32, dev, "tokens")
+    n_tokens = _out_tensor(name, n_tokens_out, (b,), torch.int32, dev, "n_tokens")
     C.annotate(bytes=float(logits.numel()) * 4 + (float(logp.numel()) * 4 if logp is not None else 0.0) + float(total) * 8,
                tag="ctc_greedy %dx%d B%d" % (total, n_classes, b))
     C.call("dle_ctc_greedy_packed", C.ptr(logits), C.ptr(logp), C.ptr(ids), C.ptr(tokens), C.ptr(n_tokens), C.ptr(cu_seqlens), b, total,
@@ -2294,23 +2293,7 @@ def conv1d_bn_packed_fwd(x, w, scale, shift, cu_in, cu_out=None, total_out=None,
         raise ValueError("%s: x must be contiguous [total,C] and w contiguous [Ko,ksize,C] of x's dtype" % name)
     total_in, c = x.shape
     ko, ks = w.shape[0], w.shape[1]
-    b = _fp_table(name, cu_in, "cu_in")
-    if cu_out is None:
-        if stride != 1:
-            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
-        cu_out = cu_in
-    elif _fp_table(name, cu_out, "cu_out") != b:
-        raise ValueError("%s: cu_in and cu_out must describe the same batch" % name)
-    if total_out is None:
-        if stride != 1:
-            raise ValueError("%s: stride %d needs cu_out and total_out" % (name, stride))
-        total_out = total_in
-    total_out = int(total_out)
-    _fp_f32(name, scale, (ko,), "scale")
-    _fp_f32(name, shift, (ko,), "shift")
-    if residual is not None and (tuple(residual.shape) != (total_out, ko) or residual.dtype != x.dtype or not residual.is_contiguous()):
-        raise ValueError("%s: residual must be a contiguous [total_out,Ko] tensor of x's dtype" % name)
-    out = _fp_out(name, out, (total_out, ko), x.dtype, x.device)
+    b, cu_out, total_out, out = _packed_conv_operands(name, x, ko, scale, shift, cu_in, cu_out, total_out, stride, residual, out)
     C.annotate(flops=2.0 * total_out * c * ko * ks, tag="conv1d_bn %dx%d k%d ks%d s%d d%d B%d" % (total_in, c, ko, ks, stride, dilation, b),
                bytes=float(x.numel() + w.numel() + out.numel() * (2 if residual is not None else 1)) * 2)
     C.call("dle_conv1d_bn_packed_fwd", C.ptr(x), C.ptr(w), C.ptr(scale), C.ptr(shift), C.ptr(residual), C.ptr(out), C.ptr(cu_in),
@@ -2359,7 +2342,7 @@ def txl_rel_attention_fwd(q, u, v, kv, r, heads, qlen, mlen, start, shift, scale
         raise ValueError("%s: q must be [B*qlen, H] with unit inner stride and a row pitch that is a multiple of 8" % name)
     if r.dim() != 2 or r.shape[1] != h or r.shape[0] < klen or not r.is_contiguous():
         raise ValueError("%s: r must be a contiguous [n_dist >= klen, H] table" % name)
-    out = _fp_out(name, out, (b * qlen, h), q.dtype, q.device)
+    out = _out_tensor(name, out, (b * qlen, h), q.dtype, q.device)
     C.annotate(flops=2.0 * b * heads * qlen * klen * 64 * 3, bytes=float(b) * (klen * 2 * h + 2 * qlen * h) * 2 + float(klen) * h * 2,
                tag="txl_attn B%d h%d q%d m%d" % (b, heads, qlen, mlen))
     C.call("dle_txl_rel_attention_fwd", C.ptr(q), q.stride(0), C.ptr(u), C.ptr(v), C.ptr(kv), C.ptr(r), C.ptr(out), b, heads, 64,
@@ -2483,9 +2466,9 @@ def tft_grn_fwd(x, p, ctx=None, rows_per_ctx=1, res=None, res_rows_per_batch=0, 
     if x_index is not None and (x_index.dtype != torch.int32 or x_index.dim() != 1 or not x_index.is_contiguous()):
         raise ValueError("%s: x_index must be a contiguous int32 vector" % name)
     _tft_w16(name, p["wg"], (2 * TFT_HIDDEN, TFT_HIDDEN), dtype, "wg")
-    _fp_f32(name, p["bg"], (2 * TFT_HIDDEN,), "bg")
-    _fp_f32(name, p["gamma"], (TFT_HIDDEN,), "gamma")
-    _fp_f32(name, p["beta"], (TFT_HIDDEN,), "beta")
+    _f32_tensor(name, p["bg"], (2 * TFT_HIDDEN,), "bg")
+    _f32_tensor(name, p["gamma"], (TFT_HIDDEN,), "gamma")
+    _f32_tensor(name, p["beta"], (TFT_HIDDEN,), "beta")
     res_ptr, ldr, res_bs = 0, 0, 0
     if gate:
         if res is None or ctx is not None:
@@ -2506,8 +2489,8 @@ def tft_grn_fwd(x, p, ctx=None, rows_per_ctx=1, res=None, res_rows_per_batch=0, 
             raise ValueError("%s: the residual of the full network is its input" % name)
         for k in ("wa", "wi"):
             _tft_w16(name, p[k], (TFT_HIDDEN, TFT_HIDDEN), dtype, k)
-        _fp_f32(name, p["ba"], (TFT_HIDDEN,), "ba")
-        _fp_f32(name, p["bi"], (TFT_HIDDEN,), "bi")
+        _f32_tensor(name, p["ba"], (TFT_HIDDEN,), "ba")
+        _f32_tensor(name, p["bi"], (TFT_HIDDEN,), "bi")
         if ctx is not None:
             if "wc" not in p:
                 raise ValueError("%s: this network has no lin_c" % name)
@@ -2520,11 +2503,11 @@ def tft_grn_fwd(x, p, ctx=None, rows_per_ctx=1, res=None, res_rows_per_batch=0, 
         nq = wq.shape[0]
         if not 1 <= nq <= 8:
             raise ValueError("%s: 1 to 8 quantiles (got %d)" % (name, nq))
-        _fp_f32(name, wq, (nq, TFT_HIDDEN), "wq")
-        _fp_f32(name, bq, (nq,), "bq")
+        _f32_tensor(name, wq, (nq, TFT_HIDDEN), "wq")
+        _f32_tensor(name, bq, (nq,), "bq")
         q = torch.empty((rows, nq), dtype=torch.float32, device=x.device)
     if want_out or q is None:
-        out = _fp_out(name, out, (rows, TFT_HIDDEN), dtype, x.device)
+        out = _out_tensor(name, out, (rows, TFT_HIDDEN), dtype, x.device)
     else:
         out = None
     C.annotate(flops=2.0 * rows * TFT_HIDDEN * TFT_HIDDEN * (2 if gate else 4 + (ctx is not None)), tag="tft_grn %d%s" % (rows, " gate" if gate else ""))
