@@ -22,7 +22,7 @@ import torch.distributed as dist
 from .. import _cabi as C
 from .. import functional as F
 from .. import multi_tensor as mt
-from ..dlrm.engine import GradScalerState
+from ..utils.amp import GradScalerState
 from ..utils.buckets import GradBuckets
 from ..utils import comm
 from .model import BertForPreTraining

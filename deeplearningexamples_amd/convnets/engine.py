@@ -25,7 +25,7 @@ import torch.distributed as dist
 
 from .. import functional as F
 from .. import multi_tensor as mt
-from ..dlrm.engine import GradScalerState
+from ..utils.amp import GradScalerState
 from ..utils.buckets import GradBuckets
 from ..utils import comm
 from .resnet import Deferred, ResNet50

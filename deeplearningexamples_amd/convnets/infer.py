@@ -16,10 +16,13 @@ before the next call at that shape.
 ResNeXtClassifier (below) serves ResNeXt101-32x4d and SE-ResNeXt101-32x4d on the same stem, 1x1 units, pooling and fc, with the
 grouped 3x3 kernel and the squeeze-and-excitation launches in the block.
 """
+import functools
+
 import torch
 
 from .. import functional as F
-from ..utils.graph import GraphedStep
+from ..utils.frontend import GraphCache, require_16bit
+from ..utils.state import fold_bn, strip_module_prefix
 from .resnet import ConvBN, ResNet50
 from .resnext import CARDINALITY, ResNeXt101, state_has_se
 
@@ -27,14 +30,6 @@ from .resnext import CARDINALITY, ResNeXt101, state_has_se
 # The place to put a unit whose fused launch measures slower than the pair; tools/rn50_infer_perf.py times whole networks only, so
 # no unit has been measured on its own and none is listed (DESIGN.md section 4h has the whole-network table).
 TWO_LAUNCH_UNITS = frozenset()
-
-
-def fold_bn(gamma, beta, running_mean, running_var, eps):
-    """Evaluation-mode BatchNorm as y = scale * x + shift, in fp32: scale = gamma * rsqrt(running_var + eps),
-    shift = beta - running_mean * scale."""
-    scale = gamma.float() * torch.rsqrt(running_var.float() + eps)
-    shift = beta.float() - running_mean.float() * scale
-    return scale.contiguous(), shift.contiguous()
 
 
 def state_from_checkpoint(obj, ema=False):
@@ -49,7 +44,7 @@ def state_from_checkpoint(obj, ema=False):
         state = obj[keys[0]]
     else:
         state = obj.get("state_dict", obj)
-    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    return strip_module_prefix(state)
 
 
 def affine_relu_maxpool(t, scale, shift, zeros, ones):
@@ -65,48 +60,68 @@ class _Unit:
     __slots__ = ("w16", "scale", "shift", "stride", "pad", "relu", "two_launch", "ones", "zeros")
 
 
+def pack_unit(u, dtype, dev):
+    """A conv + BatchNorm pair (conv, bn, k, stride, pad, relu: a resnet.ConvBN or anything shaped like it) -> _Unit on `dev`."""
+    w = u.conv.weight.data
+    ko, ci, r, s = w.shape
+    cp = (ci + 7) // 8 * 8                # (the stem's 3 channels, padded for the generic convolution route)
+    o = _Unit()
+    o.w16 = torch.zeros((ko, r, s, cp), dtype=dtype, device=dev)
+    F.cast_rows(w.permute(0, 2, 3, 1).reshape(ko * r * s, ci), dtype, cols_out=cp, out=o.w16.view(ko * r * s, cp))
+    o.scale, o.shift = fold_bn(u.bn.weight.data, u.bn.bias.data, u.bn.running_mean, u.bn.running_var, u.bn.eps)
+    o.stride, o.pad, o.relu = u.stride, u.pad, u.relu
+    o.two_launch = (u.k, u.stride, ci, ko) in TWO_LAUNCH_UNITS
+    # what the kernels of the training forward take as (mean, rstd, gamma, beta): (0, scale, 1, shift) -- the stem's pooling pass
+    # (affine_relu_maxpool) and the stand-alone apply of a two-launch unit
+    o.ones, o.zeros = torch.ones_like(o.scale), torch.zeros_like(o.scale)
+    return o
+
+
+@functools.lru_cache(maxsize=None)
+def _mean_std_255(dev):
+    """ImageNet's channel means and deviations on the 0..255 scale, one pair of fp32 [3] tensors per device."""
+    from .dataloaders import IMAGENET_MEAN, IMAGENET_STD
+    return torch.tensor(IMAGENET_MEAN, device=dev) * 255.0, torch.tensor(IMAGENET_STD, device=dev) * 255.0
+
+
+def images_nhwc(images, c_padded, dtype):
+    """NCHW images on the GPU -> 16-bit NHWC with the channels zero-padded to c_padded: fp32 images as they are, uint8 images
+    normalised on the way (one launch either way)."""
+    if images.dtype == torch.uint8:
+        mean, std = _mean_std_255(images.device)
+        return F.u8_nchw_normalize_nhwc(images, mean, std, dtype, c_padded)
+    return F.nchw_to_nhwc(images, dtype, c_padded)
+
+
 class ResNet50Classifier:
     def __init__(self, model, dtype=torch.bfloat16, device=None, graphs=False):
         """model: a ResNet50 (left untouched; nothing of it is referenced afterwards) or its state dict (any device; `module.`
         prefixes allowed).  dtype: torch.float16 or torch.bfloat16.  graphs: replay one captured graph per input shape."""
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
-                             "recipes are not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("ResNet50Classifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        require_16bit(dtype, "ResNet50Classifier")
         if not isinstance(model, ResNet50):
             state = state_from_checkpoint(model)
             dev = torch.device(device if device is not None else "cuda")
             module = ResNet50(num_classes=state["fc.weight"].shape[0], device=dev)
             module.load_state_dict(state)
             model = module
-        self.dev = model.fc.weight.device
-        self.dtype, self.graphs = dtype, bool(graphs)
-        self.num_classes = model.fc.weight.shape[0]
+        self._init_common(model.fc, dtype, graphs)
         stem, blocks = model.units()
         with torch.no_grad():
             self.stem = self._unit(stem)
             self.stem_w2 = F.stem_pack_weight(model.conv1.weight.data, dtype)
             self.blocks = [tuple(self._unit(u) if u is not None else None for u in blk) for blk in blocks]
-            self.fc_w16 = F.cast(model.fc.weight.data, dtype)
-            self.fc_bias = model.fc.bias.data.float().clone()
-        self._mean_std = None
-        self._graphs = {}                     # (input shape, input dtype) -> GraphedStep
+
+    def _init_common(self, fc, dtype, graphs):
+        """What the three classifiers keep of the last layer `fc`, and their graph cache."""
+        self.dev, self.dtype = fc.weight.device, dtype
+        self.num_classes = fc.weight.shape[0]
+        with torch.no_grad():
+            self.fc_w16 = F.cast(fc.weight.data, dtype)
+            self.fc_bias = fc.bias.data.float().clone()
+        self._graphs = GraphCache(graphs)     # (input shape, input dtype) -> GraphedStep
 
     def _unit(self, u):
-        w = u.conv.weight.data
-        ko, ci, r, s = w.shape
-        cp = (ci + 7) // 8 * 8                # (the stem's 3 channels, padded for the generic convolution route)
-        o = _Unit()
-        o.w16 = torch.zeros((ko, r, s, cp), dtype=self.dtype, device=self.dev)
-        F.cast_rows(w.permute(0, 2, 3, 1).reshape(ko * r * s, ci), self.dtype, cols_out=cp, out=o.w16.view(ko * r * s, cp))
-        o.scale, o.shift = fold_bn(u.bn.weight.data, u.bn.bias.data, u.bn.running_mean, u.bn.running_var, u.bn.eps)
-        o.stride, o.pad, o.relu = u.stride, u.pad, u.relu
-        o.two_launch = (u.k, u.stride, ci, ko) in TWO_LAUNCH_UNITS
-        # what the kernels of the training forward take as (mean, rstd, gamma, beta): (0, scale, 1, shift) -- the stem's pooling pass
-        # (affine_relu_maxpool) and the stand-alone apply of a two-launch unit
-        o.ones, o.zeros = torch.ones_like(o.scale), torch.zeros_like(o.scale)
-        return o
+        return pack_unit(u, self.dtype, self.dev)
 
     @classmethod
     def from_checkpoint(cls, path, ema=False, **kw):
@@ -127,14 +142,7 @@ class ResNet50Classifier:
         h, w = images.shape[-2:]
         p, q = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         stem4 = w <= 224 and p % 2 == 0 and q % 2 == 0
-        cp = 4 if stem4 else 8
-        if images.dtype == torch.uint8:
-            if self._mean_std is None:
-                from .dataloaders import IMAGENET_MEAN, IMAGENET_STD
-                self._mean_std = (torch.tensor(IMAGENET_MEAN, device=self.dev) * 255.0, torch.tensor(IMAGENET_STD, device=self.dev) * 255.0)
-            x = F.u8_nchw_normalize_nhwc(images, self._mean_std[0], self._mean_std[1], self.dtype, cp)
-        else:
-            x = F.nchw_to_nhwc(images, self.dtype, cp)
+        x = images_nhwc(images, 4 if stem4 else 8, self.dtype)
         u = self.stem
         if stem4:
             # the stem's own kernel without statistics, then affine + ReLU + 3x3/2 max pooling in one pass: the 112x112x64
@@ -149,7 +157,9 @@ class ResNet50Classifier:
         for (u1, u2, u3, ud) in self.blocks:
             res = self._run(ud, h) if ud is not None else h
             h = self._run(u3, self._run(u2, self._run(u1, h)), residual=res)
-        pooled = F.avgpool_fwd(h)
+        return self._fc(F.avgpool_fwd(h))
+
+    def _fc(self, pooled):
         return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
                       out_dtype=torch.float32, bias=self.fc_bias)
 
@@ -164,13 +174,7 @@ class ResNet50Classifier:
         if not images.is_contiguous():
             images = images.contiguous()          # --memory-format nhwc loaders hand over channels_last tensors
         with torch.no_grad():
-            if not self.graphs:
-                return self._forward(images)
-            key = (tuple(images.shape), images.dtype)
-            g = self._graphs.get(key)
-            if g is None:
-                g = self._graphs[key] = GraphedStep(self._forward, warmup_steps=2)
-            return g(images)
+            return self._graphs.run((tuple(images.shape), images.dtype), self._forward, images)
 
     def predict(self, images, topk=5):
         """-> (softmax probabilities [N, classes] fp32, the indices [N, topk] of the most probable classes, most probable first)."""
@@ -194,29 +198,19 @@ class ResNeXtClassifier(ResNet50Classifier):
     def __init__(self, model, dtype=torch.bfloat16, device=None, graphs=False):
         """model: a ResNeXt101 (left untouched) or a state dict of either architecture (any device; `module.` prefixes allowed; the
         SE variant is recognised by its squeeze weights)."""
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
-                             "recipes are not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("ResNeXtClassifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        require_16bit(dtype, "ResNeXtClassifier")
         if not isinstance(model, ResNeXt101):
             state = state_from_checkpoint(model)
             dev = torch.device(device if device is not None else "cuda")
             module = ResNeXt101(num_classes=state["fc.weight"].shape[0], se=state_has_se(state), device=dev)
             module.load_state_dict(state)
             model = module
-        self.dev = model.fc.weight.device
-        self.dtype, self.graphs = dtype, bool(graphs)
-        self.num_classes = model.fc.weight.shape[0]
+        self._init_common(model.fc, dtype, graphs)
         self.se = model.se
         with torch.no_grad():
             self.stem = self._unit(ConvBN(model.conv1, model.bn1, "conv1", "bn1", relu=True))
             self.stem_w2 = F.stem_pack_weight(model.conv1.weight.data, dtype)
             self.blocks = [self._block(blk) for blk in model.bottlenecks()]
-            self.fc_w16 = F.cast(model.fc.weight.data, dtype)
-            self.fc_bias = model.fc.bias.data.float().clone()
-        self._mean_std = None
-        self._graphs = {}
 
     def _block(self, blk):
         b = _Block()
@@ -246,9 +240,7 @@ class ResNeXtClassifier(ResNet50Classifier):
             else:
                 t = self._run(b.u3, t)
                 h = F.se_apply(t, F.se_gate(t, *b.se), residual=res, relu=True)
-        pooled = F.avgpool_fwd(h)
-        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
-                      out_dtype=torch.float32, bias=self.fc_bias)
+        return self._fc(F.avgpool_fwd(h))
 
     def eval_step(self, images, target):
         """-> (loss [1] (plain cross entropy, like ResNetTrainer.eval_step), fp32 logits)."""
@@ -278,30 +270,19 @@ class EfficientNetClassifier(ResNet50Classifier):
         (any device; `module.` prefixes and the published files' `layerN.` spelling allowed; original versus wide-SE is recognised
         from the squeeze weights' shapes)."""
         from . import efficientnet as E
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
-                             "recipes are not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("EfficientNetClassifier: dtype must be torch.float16 or torch.bfloat16 (got %s)" % dtype)
+        require_16bit(dtype, "EfficientNetClassifier")
         if not isinstance(model, E.EfficientNet):
             state = E.remap_ngc(state_from_checkpoint(model))
             dev = torch.device(device if device is not None else "cuda")
             module = E.build(E.arch_from_state(state), num_classes=state["classifier.fc.weight"].shape[0], device=dev)
             module.load_state_dict(state)
             model = module
-        fc = model.classifier.fc
-        self.dev = fc.weight.device
-        self.dtype, self.graphs = dtype, bool(graphs)
-        self.num_classes = fc.weight.shape[0]
+        self._init_common(model.classifier.fc, dtype, graphs)
         self.arch = model.arch
         with torch.no_grad():
             self.stem = self._cb(model.stem)
             self.blocks = [self._block(blk, first=i == 0) for i, blk in enumerate(model.mbconv_blocks())]
             self.features = self._cb(model.features)
-            self.fc_w16 = F.cast(fc.weight.data, dtype)
-            self.fc_bias = fc.bias.data.float().clone()
-        self._mean_std = None
-        self._graphs = {}
 
     def _cb(self, seq):
         """A conv + BatchNorm pair of the module tree -> _Unit, never with a ReLU: the SiLU behind it is its reader's."""
@@ -324,22 +305,13 @@ class EfficientNetClassifier(ResNet50Classifier):
         return b
 
     def _forward(self, images):
-        if images.dtype == torch.uint8:
-            if self._mean_std is None:
-                from .dataloaders import IMAGENET_MEAN, IMAGENET_STD
-                self._mean_std = (torch.tensor(IMAGENET_MEAN, device=self.dev) * 255.0, torch.tensor(IMAGENET_STD, device=self.dev) * 255.0)
-            x = F.u8_nchw_normalize_nhwc(images, self._mean_std[0], self._mean_std[1], self.dtype, 8)
-        else:
-            x = F.nchw_to_nhwc(images, self.dtype, 8)
-        h = self._run(self.stem, x)
+        h = self._run(self.stem, images_nhwc(images, 8, self.dtype))
         for b in self.blocks:
             t = h if b.expand is None else self._run(b.expand, h)
             t, pool = F.dwconv2d_act_fwd(t, b.w_dw, b.scale_dw, b.shift_dw, b.stride, in_act=b.in_act, out_act=True, pool=True)
             gate = F.se_gate_act(pool, 1.0 / (t.shape[1] * t.shape[2]), *b.se, act="silu")
             t = F.se_apply(t, gate, residual=None, relu=False)
             h = self._run(b.proj, t, residual=h if b.residual else None)
-        pooled = F.silu_avgpool_fwd(self._run(self.features, h))
-        return F.gemm(pooled, self.fc_w16, pooled.shape[0], self.fc_w16.shape[0], self.fc_w16.shape[1], True, True,
-                      out_dtype=torch.float32, bias=self.fc_bias)
+        return self._fc(F.silu_avgpool_fwd(self._run(self.features, h)))
 
     eval_step = ResNeXtClassifier.eval_step

@@ -32,6 +32,7 @@ import torch.distributed as dist
 from .. import functional as F
 from .. import multi_tensor as mt
 from ..utils import comm
+from ..utils.amp import GradScalerState
 from ..utils.comm import allreduce_mean_
 from .model import DistributedDlrm
 from .placement import ExchangePlan
@@ -45,25 +46,6 @@ def optimizer_plan(lr, world, adam_embeddings=False, adam_mlps=False):
     return {"embeddings": (lr, world) if adam_embeddings else (lr / world, 1),
             "bottom_mlp": (lr, world) if adam_mlps else (lr / world, 1),
             "top_mlp": (lr, 1)}
-
-
-class GradScalerState:
-    """Device-resident loss-scale state (torch.cuda.amp.GradScaler semantics, main.py:497)."""
-
-    def __init__(self, device, enabled=True, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5,
-                 growth_interval=int(1e9)):
-        self.enabled = enabled
-        self.growth_factor, self.backoff_factor, self.growth_interval = growth_factor, backoff_factor, growth_interval
-        s = init_scale if enabled else 1.0
-        self.scale = torch.full((1,), s, dtype=torch.float32, device=device)
-        self.inv_scale = torch.full((1,), 1.0 / s, dtype=torch.float32, device=device)
-        self.found_inf = torch.zeros(1, dtype=torch.float32, device=device)
-        self.growth_tracker = torch.zeros(1, dtype=torch.int32, device=device)
-
-    def update(self):
-        if self.enabled:
-            F.amp_update_scale_(self.scale, self.growth_tracker, self.found_inf, self.inv_scale,
-                                self.growth_factor, self.backoff_factor, min(self.growth_interval, 2 ** 31 - 1))
 
 
 class _FlatGrads:

@@ -27,8 +27,8 @@ a text or a predicted spectrogram longer than 1024 rows (the envelope of the pac
 import numpy as np
 import torch
 
-from .. import _cabi as C
 from .. import functional as F
+from ..utils.frontend import gpu_device, require_16bit
 from .model import LJSPEECH_PITCH, LN_EPS, MAX_ROWS, FastPitchModel, check_config, normalize_keys, positional_table
 
 
@@ -44,11 +44,7 @@ class FastPitchSynthesizer:
     def __init__(self, model_or_state, config=None, dtype=torch.float16, device=None):
         """model_or_state: a FastPitchModel (left untouched) or the reference's state dict (then `config` holds the reference's
         config keys; missing ones take the defaults of fastpitch/arg_parser.py).  dtype: torch.float16 or torch.bfloat16."""
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
-                             "recipes are not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("dtype must be torch.float16 or torch.bfloat16 (got %s)" % (dtype,))
+        require_16bit(dtype, "FastPitchSynthesizer")
         if isinstance(model_or_state, FastPitchModel):
             model = model_or_state
         else:
@@ -61,9 +57,7 @@ class FastPitchSynthesizer:
             raise ValueError("pitch_conditioning_formants = %d: only 1 is built" % cfg["pitch_conditioning_formants"])
         if cfg.get("pre_lnorm"):
             raise ValueError("pre_lnorm: the pre-LayerNorm variant of the FFT block is not built")
-        self.dev = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise C.DleError("FastPitchSynthesizer runs on the MI355X only (got device %s); there is no CPU path" % dev)
+        self.dev = dev = gpu_device(device, "FastPitchSynthesizer")
         self.dtype = dtype
         self.d = d = cfg["symbols_embedding_dim"]
         self.n_mel = cfg["n_mel_channels"]

@@ -13,6 +13,8 @@ import collections
 
 import torch
 
+from ..utils.state import ParamTable, strip_module_prefix
+
 # fastpitch/arg_parser.py:38-128 (and train.py's --n-speakers 1); n_symbols / padding_idx: the english_basic symbol set
 DEFAULT_CONFIG = dict(
     n_mel_channels=80, n_symbols=148, padding_idx=0, symbols_embedding_dim=384,
@@ -115,13 +117,7 @@ def ignored_key(k):
 
 def normalize_keys(state):
     """`module.` prefixes stripped (models.py:226), the ignored keys dropped."""
-    out = collections.OrderedDict()
-    for k, v in state.items():
-        while k.startswith("module."):
-            k = k[len("module."):]
-        if not ignored_key(k):
-            out[k] = v
-    return out
+    return collections.OrderedDict((k, v) for k, v in strip_module_prefix(state).items() if not ignored_key(k))
 
 
 def positional_table(n_pos, d_model):
@@ -132,29 +128,11 @@ def positional_table(n_pos, d_model):
     return torch.cat([sinusoid.sin(), sinusoid.cos()], dim=1)
 
 
-class FastPitchModel:
+class FastPitchModel(ParamTable):
     """The parameters as fp32 tensors on `device`, zero until loaded."""
+    NAME = "FastPitch"
+    normalize_keys = staticmethod(normalize_keys)
 
     def __init__(self, config, device="cpu"):
         self.cfg = check_config(config)
-        self.device = torch.device(device)
-        self.params = collections.OrderedDict((k, torch.zeros(s, dtype=torch.float32, device=self.device))
-                                              for k, s in state_shapes(self.cfg).items())
-
-    def state_dict(self):
-        return collections.OrderedDict(self.params)
-
-    def load_state_dict(self, state):
-        state = normalize_keys(state)
-        want = state_shapes(self.cfg)
-        missing = [k for k in want if k not in state]
-        if missing:
-            raise KeyError("FastPitch state lacks %s" % ", ".join(missing[:8]))
-        for k, v in state.items():
-            if k not in want:
-                raise KeyError("unexpected key %r in a FastPitch state" % k)
-            v = v.detach().to(self.device, torch.float32)
-            if tuple(v.shape) != tuple(want[k]):
-                raise ValueError("%s: shape %s, expected %s" % (k, tuple(v.shape), tuple(want[k])))
-            self.params[k] = v.clone()
-        return self
+        super().__init__(state_shapes(self.cfg), device)

@@ -21,7 +21,7 @@ import torch
 
 from .. import _cabi as C
 from .. import functional as F
-from ..utils.graph import GraphedStep
+from ..utils.frontend import GraphCache, gpu_device, require_16bit
 from ..waveglow.infer import STFT
 from ..waveglow.infer import Denoiser as _WaveGlowDenoiser
 from .model import LRELU_SLOPE, N_MEL, HifiGanGenerator, check_config, normalize_keys
@@ -42,11 +42,7 @@ class HifiGanVocoder:
         """model_or_state: a HifiGanGenerator (left untouched) or the reference's generator state dict (then `config` is
         required; any device; `module.` prefixes, the older flat resblock keys and folded `weight` tensors allowed).
         dtype: torch.float16 or torch.bfloat16.  graphs: replay one captured graph per (B, T)."""
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (the reference's fp32 / TF32 "
-                             "recipes are not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("dtype must be torch.float16 or torch.bfloat16 (got %s)" % (dtype,))
+        require_16bit(dtype, "HifiGanVocoder")
         if isinstance(model_or_state, HifiGanGenerator):
             model = model_or_state
         else:
@@ -54,10 +50,8 @@ class HifiGanVocoder:
                 raise ValueError("a state dict needs its config (upsample_rates, ..., resblock_dilation_sizes)")
             model = HifiGanGenerator(config, device="cpu").load_state_dict(model_or_state)
         self.cfg = cfg = check_config(model.cfg)
-        self.dev = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise C.DleError("HifiGanVocoder runs on the MI355X only (got device %s); there is no CPU path" % dev)
-        self.dtype, self.graphs = dtype, bool(graphs)
+        self.dev = dev = gpu_device(device, "HifiGanVocoder")
+        self.dtype = dtype
         self.rates = list(cfg["upsample_rates"])
         self.hop = 1
         for u in self.rates:
@@ -93,7 +87,7 @@ class HifiGanVocoder:
             self.post_bias = model.params["conv_post.bias"].float().contiguous().to(dev)
             self.post_c = post.cin
         self._buffers = {}
-        self._graphs = {}                     # (B, T) -> GraphedStep
+        self._graphs = GraphCache(graphs)     # (B, T) -> GraphedStep
 
     @classmethod
     def from_checkpoint(cls, path_or_ckpt, ema=False, config=None, **kw):
@@ -118,7 +112,7 @@ class HifiGanVocoder:
         key = (b, t)
         w = self._buffers.get(key)
         if w is None:
-            if not self.graphs:               # eager: the buffers of ONE shape, the most recent (a captured graph owns its shape's)
+            if not self._graphs.graphs:       # eager: the buffers of ONE shape, the most recent (a captured graph owns its shape's)
                 self._buffers.clear()
             def e(*shape, dtype=self.dtype):
                 return torch.empty(shape, dtype=dtype, device=self.dev)
@@ -176,12 +170,7 @@ class HifiGanVocoder:
             return torch.empty((0, t * self.hop), dtype=torch.float32, device=self.dev)
         mel = mel.float().contiguous()                                   # (a 16-bit spectrogram widens exactly)
         with torch.no_grad():
-            if not self.graphs:
-                return self._forward(mel)
-            g = self._graphs.get((b, t))
-            if g is None:
-                g = self._graphs[(b, t)] = GraphedStep(self._forward, warmup_steps=2)
-            return g(mel)
+            return self._graphs.run((b, t), self._forward, mel)
 
     __call__ = infer
 

@@ -8,6 +8,8 @@ import collections
 
 import torch
 
+from ..utils.state import ParamTable, strip_module_prefix
+
 N_MEL = 80
 LRELU_SLOPE = 0.1
 CONFIG_KEYS = ("upsample_rates", "upsample_kernel_sizes", "upsample_initial_channel", "resblock", "resblock_kernel_sizes",
@@ -73,9 +75,7 @@ def normalize_keys(state):
     """`module.` prefixes stripped and the older flat `resblocks.N.` keys mapped to `resblocks.N//3.N%3.`, the constant 3 as in
     Generator.load_state_dict (models.py:182-206)."""
     out = collections.OrderedDict()
-    for k, v in state.items():
-        while k.startswith("module."):
-            k = k[len("module."):]
+    for k, v in strip_module_prefix(state).items():
         if k.startswith("resblocks."):
             parts = k.split(".")
             if len(parts) == 5:
@@ -85,26 +85,21 @@ def normalize_keys(state):
     return out
 
 
-class HifiGanGenerator:
+class HifiGanGenerator(ParamTable):
     """The generator's parameters as fp32 tensors on `device`: weight_g / weight_v / bias per layer, zero until loaded."""
 
     def __init__(self, config, device="cpu"):
         self.cfg = check_config(config)
         self.layers = layers(self.cfg)
-        self.device = torch.device(device)
         self.folded = {}                      # layer name -> folded fp32 weight, for a checkpoint saved after remove_weight_norm
-        self.params = collections.OrderedDict((k, torch.zeros(s, dtype=torch.float32, device=self.device))
-                                              for k, s in state_shapes(self.cfg).items())
-
-    def state_dict(self):
-        return collections.OrderedDict(self.params)
+        super().__init__(state_shapes(self.cfg), device)
 
     def load_state_dict(self, state):
         """The reference's generator state: weight-normed (weight_g + weight_v) or folded (`weight`, saved after
         remove_weight_norm: kept as it is, folded_weight() returns it), nested or flat resblock keys, `module.` prefixes,
         weights with a trailing unit dimension more or less (the reference's Conv1d / Conv2d fix-up)."""
         state = normalize_keys(state)
-        want = state_shapes(self.cfg)
+        want = self.shapes
         self.folded = {}
         seen = set()
         for k, v in state.items():

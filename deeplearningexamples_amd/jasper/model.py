@@ -19,9 +19,8 @@ false` hand on their output alone, so the list starts again behind them.
 import collections
 import re
 
-import torch
-
-from ..quartznet.model import _bn_shapes, _one, apply_overrides, load_config, normalize_keys      # noqa: F401 (re-exported)
+from ..quartznet.model import QuartzNetModel, _bn_shapes, _one, apply_overrides      # noqa: F401 (apply_overrides: for the CLI)
+from ..utils.state import strip_module_prefix
 
 BN_EPS = 1e-3                  # model.py:131
 BLOCK_KEYS = ("filters", "repeat", "kernel_size", "stride", "dilation", "padding", "dropout", "residual", "residual_dense")
@@ -134,36 +133,11 @@ def convert_v1_state_dict(state):
     return out
 
 
-class JasperModel:
-    """The parameters as fp32 tensors (num_batches_tracked int64) on `device`, zero until loaded (running_var one)."""
+class JasperModel(QuartzNetModel):
+    """QuartzNetModel over Jasper's configuration and names; a state's keys of the first release are converted on the way in."""
+    NAME = "Jasper"
+    check_config, state_shapes = staticmethod(check_config), staticmethod(state_shapes)
 
-    def __init__(self, cfg, device="cpu"):
-        self.cfg = load_config(cfg)
-        self.labels, self.features, self.blocks = check_config(self.cfg)
-        self.device = torch.device(device)
-        self.params = collections.OrderedDict()
-        for k, shape in state_shapes(self.cfg).items():
-            if k.endswith("num_batches_tracked"):
-                self.params[k] = torch.zeros(shape, dtype=torch.int64, device=self.device)
-            elif k.endswith("running_var"):
-                self.params[k] = torch.ones(shape, dtype=torch.float32, device=self.device)
-            else:
-                self.params[k] = torch.zeros(shape, dtype=torch.float32, device=self.device)
-
-    def state_dict(self):
-        return collections.OrderedDict(self.params)
-
-    def load_state_dict(self, state):
-        state = convert_v1_state_dict(normalize_keys(state))
-        want = state_shapes(self.cfg)
-        missing = [k for k in want if k not in state and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError("Jasper state lacks %s" % ", ".join(missing[:8]))
-        for k, v in state.items():
-            if k not in want:
-                raise KeyError("unexpected key %r in a Jasper state" % k)
-            v = torch.as_tensor(v).detach().to(self.device, self.params[k].dtype)
-            if tuple(v.shape) != tuple(want[k]):
-                raise ValueError("%s: shape %s, expected %s" % (k, tuple(v.shape), tuple(want[k])))
-            self.params[k] = v.clone()
-        return self
+    @staticmethod
+    def normalize_keys(state):
+        return convert_v1_state_dict(strip_module_prefix(state))

@@ -31,8 +31,9 @@ import torch
 
 from ..tacotron2.audio import load_wav_to_torch
 from ..utils import dllogger as DLLogger
+from ..utils.state import load_config
 from .infer import QuartzNetRecognizer
-from .model import apply_overrides, load_config
+from .model import apply_overrides
 
 
 def build_parser():

@@ -13,22 +13,12 @@ A container, not a module: it holds the tensors of `QuartzNet(encoder_kw, decode
 -- and has no forward: that lives in quartznet/infer.py.
 """
 import collections
-import copy
 
-import torch
+from ..utils.state import ParamTable, load_config
 
 BN_EPS = 1e-3                  # model.py:240
 BLOCK_KEYS = ("filters", "repeat", "kernel_size", "kernel_size_factor", "stride", "dilation", "padding", "dropout", "residual",
               "residual_dense", "groups", "separable", "heads", "normalization", "norm_groups")
-
-
-def load_config(path_or_cfg):
-    """The reference's YAML file (or the dict it holds) -> a deep copy as a dict."""
-    if isinstance(path_or_cfg, dict):
-        return copy.deepcopy(path_or_cfg)
-    import yaml
-    with open(path_or_cfg) as f:
-        return yaml.safe_load(f)
 
 
 def apply_overrides(cfg, overrides):
@@ -154,46 +144,14 @@ def state_shapes(cfg):
     return s
 
 
-def normalize_keys(state):
-    """`module.` prefixes (DistributedDataParallel) stripped."""
-    out = collections.OrderedDict()
-    for k, v in state.items():
-        while k.startswith("module."):
-            k = k[len("module."):]
-        out[k] = v
-    return out
-
-
-class QuartzNetModel:
-    """The parameters as fp32 tensors (num_batches_tracked int64) on `device`, zero until loaded (running_var one)."""
+class QuartzNetModel(ParamTable):
+    """The parameters as fp32 tensors (num_batches_tracked int64) on `device`, zero until loaded (running_var one).  A subclass
+    for another network of the family replaces NAME, check_config, state_shapes and normalize_keys."""
+    NAME = "QuartzNet"
+    ABSENT_OK = ("num_batches_tracked",)
+    check_config, state_shapes = staticmethod(check_config), staticmethod(state_shapes)
 
     def __init__(self, cfg, device="cpu"):
         self.cfg = load_config(cfg)
-        self.labels, self.features, self.blocks = check_config(self.cfg)
-        self.device = torch.device(device)
-        self.params = collections.OrderedDict()
-        for k, shape in state_shapes(self.cfg).items():
-            if k.endswith("num_batches_tracked"):
-                self.params[k] = torch.zeros(shape, dtype=torch.int64, device=self.device)
-            elif k.endswith("running_var"):
-                self.params[k] = torch.ones(shape, dtype=torch.float32, device=self.device)
-            else:
-                self.params[k] = torch.zeros(shape, dtype=torch.float32, device=self.device)
-
-    def state_dict(self):
-        return collections.OrderedDict(self.params)
-
-    def load_state_dict(self, state):
-        state = normalize_keys(state)
-        want = state_shapes(self.cfg)
-        missing = [k for k in want if k not in state and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError("QuartzNet state lacks %s" % ", ".join(missing[:8]))
-        for k, v in state.items():
-            if k not in want:
-                raise KeyError("unexpected key %r in a QuartzNet state" % k)
-            v = torch.as_tensor(v).detach().to(self.device, self.params[k].dtype)
-            if tuple(v.shape) != tuple(want[k]):
-                raise ValueError("%s: shape %s, expected %s" % (k, tuple(v.shape), tuple(want[k])))
-            self.params[k] = v.clone()
-        return self
+        self.labels, self.features, self.blocks = self.check_config(self.cfg)
+        super().__init__(self.state_shapes(self.cfg), device)

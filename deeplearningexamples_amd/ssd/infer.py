@@ -13,8 +13,8 @@ import types
 import torch
 
 from .. import functional as F
-from ..convnets.infer import ResNet50Classifier, _Unit
-from ..utils.graph import GraphedStep
+from ..convnets.infer import _Unit, images_nhwc, pack_unit
+from ..utils.frontend import GraphCache, require_16bit
 from . import model as M
 
 # Output channels of a head launch are zero-padded to a multiple of this: 340 / 510 become 384 / 512, which puts the 3x3 / pad 1 heads
@@ -28,15 +28,14 @@ class SSDDetector:
         """model: an ssd.model.SSD300 (left untouched) or a state dict / the reference's checkpoint dict (any device; `module.`
         prefixes allowed; the width is read from the stem).  dtype: torch.float16 or torch.bfloat16.  graphs: replay one captured
         graph per (input shape, call).  dboxes: the DefaultBoxes of the geometry (default: dboxes300_coco)."""
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("SSDDetector: dtype must be torch.float16 or torch.bfloat16 (got %s): this path computes in 16 bits" % dtype)
+        require_16bit(dtype, "SSDDetector")
         if not isinstance(model, M.SSD300):
             state = M.state_from_checkpoint(model)
             module = M.SSD300("resnet50", width=M.width_from_state(state), label_num=state["conf.0.weight"].shape[0] // M.NUM_DEFAULTS[0])
             module.load_state_dict(state)
             model = module.to(torch.device(device if device is not None else "cuda"))
         self.dev = model.loc[0].weight.device
-        self.dtype, self.graphs = dtype, bool(graphs)
+        self.dtype = dtype
         self.label_num = model.label_num
         self.num_defaults = list(model.num_defaults)
         self.head_pad = int(head_pad or HEAD_PAD)
@@ -57,12 +56,11 @@ class SSDDetector:
         self.dboxes = dboxes if dboxes is not None else M.dboxes300_coco()
         self.dboxes_xywh = self.dboxes("xywh").to(self.dev).contiguous()
         self.scale_xy, self.scale_wh = self.dboxes.scale_xy, self.dboxes.scale_wh
-        self._mean_std = None
-        self._graphs = {}
+        self._graphs = GraphCache(graphs)     # (call, input shape, input dtype, the call's scalars) -> GraphedStep
 
     def _cb(self, conv, bn, relu):
         u = types.SimpleNamespace(conv=conv, bn=bn, stride=conv.stride[0], pad=conv.padding[0], relu=relu, k=conv.kernel_size[0])
-        return ResNet50Classifier._unit(self, u)
+        return pack_unit(u, self.dtype, self.dev)
 
     def _head(self, loc, conf):
         """One unit for both heads of a map: rows [0, 4 nd) are loc's filters, [4 nd, 4 nd + L nd) conf's, then zero rows."""
@@ -92,14 +90,7 @@ class SSDDetector:
 
     def _heads(self, images):
         """-> the six 16-bit NHWC head tensors [N, fs, fs, pad(nd * (4 + L))]."""
-        if images.dtype == torch.uint8:
-            if self._mean_std is None:
-                from ..convnets.dataloaders import IMAGENET_MEAN, IMAGENET_STD
-                self._mean_std = (torch.tensor(IMAGENET_MEAN, device=self.dev) * 255.0, torch.tensor(IMAGENET_STD, device=self.dev) * 255.0)
-            x = F.u8_nchw_normalize_nhwc(images, self._mean_std[0], self._mean_std[1], self.dtype, 8)
-        else:
-            x = F.nchw_to_nhwc(images, self.dtype, 8)
-        h = F.maxpool_fwd(self._run(self.stem, x))[0]
+        h = F.maxpool_fwd(self._run(self.stem, images_nhwc(images, 8, self.dtype)))[0]
         for (u1, u2, u3, ud) in self.blocks:
             res = self._run(ud, h) if ud is not None else h
             h = self._run(u3, self._run(u2, self._run(u1, h)), residual=res)
@@ -128,13 +119,7 @@ class SSDDetector:
     def _call(self, tag, fn, images, *scalars):
         images = self._check(images)
         with torch.no_grad():
-            if not self.graphs:
-                return fn(images, *scalars)
-            key = (tag, tuple(images.shape), images.dtype) + scalars
-            g = self._graphs.get(key)
-            if g is None:
-                g = self._graphs[key] = GraphedStep(lambda im: fn(im, *scalars), warmup_steps=2)
-            return g(images)
+            return self._graphs.run((tag, tuple(images.shape), images.dtype) + scalars, lambda im: fn(im, *scalars), images)
 
     def head_outputs(self, images):
         """The six head tensors as the kernels wrote them (16-bit NHWC, zero-padded channels behind nd * (4 + L))."""

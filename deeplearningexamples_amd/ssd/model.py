@@ -18,6 +18,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..utils.state import strip_module_prefix
+
 BACKBONES = ("resnet18", "resnet34", "resnet50", "resnet101", "resnet152")
 NUM_DEFAULTS = (4, 6, 6, 6, 4, 4)
 LABEL_NUM = 81
@@ -159,7 +161,7 @@ def state_from_checkpoint(obj):
     if not isinstance(obj, dict):
         raise ValueError("not a checkpoint: expected a dict, got %s" % type(obj).__name__)
     state = obj["model"] if "model" in obj and isinstance(obj["model"], dict) else obj
-    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    return strip_module_prefix(state)
 
 
 def width_from_state(state):

@@ -25,7 +25,7 @@ import torch
 from .. import _cabi as C
 from .. import functional as F
 from .. import multi_tensor as mt
-from ..dlrm.engine import GradScalerState
+from ..utils.amp import GradScalerState
 from ..utils.buckets import GradBuckets
 from ..waveglow import ops as wops
 from ..waveglow.model import FlatViews

@@ -26,9 +26,8 @@ example lengths above 192, fp32.  No CPU path.
 """
 import torch
 
-from .. import _cabi as C
 from .. import functional as F
-from ..utils.graph import GraphedStep
+from ..utils.frontend import GraphCache, gpu_device, require_16bit
 from .model import LN_EPS, TemporalFusionTransformer
 
 
@@ -40,13 +39,10 @@ class TFTForecaster:
     def __init__(self, model, dtype=torch.float16, device=None, graphs=False):
         """model: a TemporalFusionTransformer (left untouched).  Weights are packed once, here.  graphs: replay one captured graph
         per (batch size, T, explain); the chain is one stream, no branches."""
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (got %s)" % (dtype,))
+        require_16bit(dtype, "TFTForecaster")
         if not isinstance(model, TemporalFusionTransformer):
             raise TypeError("model must be a TemporalFusionTransformer")
-        self.dev = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise C.DleError("TFTForecaster runs on the MI355X only (got device %s); there is no CPU path" % dev)
+        self.dev = dev = gpu_device(device, "TFTForecaster")
         sd = {k: v.detach() for k, v in model.state_dict().items()}
         back = model.TFTpart2
         H = back.quantile_proj.in_features
@@ -55,7 +51,7 @@ class TFTForecaster:
         if back.attention.n_head != 4:
             raise ValueError("TFTForecaster: the attention kernel is built for 4 heads (got %d)" % back.attention.n_head)
         self.dtype, self.enc = dtype, int(model.encoder_length)
-        self.graphs, self._graphs = bool(graphs), {}
+        self._graphs = GraphCache(graphs)     # (B, T, explain) -> GraphedStep
         emb = model.embedding
         n_cat = len(emb.s_cat_embed) if emb.s_cat_embed is not None else 0
         n_scont = emb.s_cont_embedding_vectors.shape[0] if emb.s_cont_embedding_vectors is not None else 0
@@ -120,13 +116,8 @@ class TFTForecaster:
             static = batch["s_cat"][:, 0, 0].to(device=self.dev, dtype=torch.int32).contiguous()
         else:
             static = self._f32(batch["s_cont"])
-        if not self.graphs:
-            return self._run(static, known, observed, target, explain)
-        key = (B, T, bool(explain))
-        g = self._graphs.get(key)
-        if g is None:
-            g = self._graphs[key] = GraphedStep(lambda s, k, o, t: self._run(s, k, o, t, explain), warmup_steps=2)
-        return g(static, known, observed, target)
+        return self._graphs.run((B, T, bool(explain)), lambda s, k, o, t: self._run(s, k, o, t, explain),
+                                static, known, observed, target)
 
     def _run(self, static, known, observed, target, explain):
         H, enc, dt = F.TFT_HIDDEN, self.enc, self.dtype

@@ -79,7 +79,7 @@ def get_parser(config=None):
 
 def load_yaml_section(config_file, config):
     """eval.py:56-60: the `eval` section of entry `config` of the reference's YAML (anchors and merge keys included)."""
-    from ..quartznet.model import load_config
+    from ..utils.state import load_config
     doc = load_config(config_file)
     if config not in doc or "eval" not in (doc[config] or {}):
         raise SystemExit("--config %s: %s has no such entry with an `eval` section" % (config, config_file))

@@ -39,6 +39,7 @@ import torch
 
 from .. import _cabi as C
 from .. import functional as F
+from ..utils.frontend import gpu_device, require_16bit
 from .model import TransformerXLModel
 
 LN_EPS = 1e-5          # nn.LayerNorm's default, which the reference uses
@@ -51,10 +52,7 @@ class _Layer:
 class TransformerXLEvaluator:
     def __init__(self, model, batch_size, tgt_len=None, mem_len=None, dtype=torch.float16, device=None):
         """model: a TransformerXLModel (left untouched).  tgt_len / mem_len default to the configuration's."""
-        if dtype == torch.float32:
-            raise ValueError("this path computes in 16 bits: pass torch.float16 or torch.bfloat16 (fp32 is not built)")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("dtype must be torch.float16 or torch.bfloat16 (got %s)" % (dtype,))
+        require_16bit(dtype, "TransformerXLEvaluator")
         if not isinstance(model, TransformerXLModel):
             raise TypeError("model must be a TransformerXLModel")
         cfg = self.cfg = model.cfg
@@ -67,9 +65,7 @@ class TransformerXLEvaluator:
         if not F.txl_attention_supported(self.tgt_len, self.cap, cfg["d_head"]):
             raise ValueError("tgt_len %d with mem_len %d is outside the attention kernel's envelope (tgt_len <= 512, "
                              "mem_len + tgt_len <= 4096)" % (self.tgt_len, self.mem_len))
-        self.dev = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise C.DleError("TransformerXLEvaluator runs on the MI355X only (got device %s); there is no CPU path" % dev)
+        self.dev = dev = gpu_device(device, "TransformerXLEvaluator")
         self.dtype = dtype
         self.nh, self.H, self.d_model = cfg["n_head"], cfg["n_head"] * cfg["d_head"], cfg["d_model"]
         self.scale = 1.0 / math.sqrt(cfg["d_head"])

@@ -24,7 +24,7 @@ import torch
 from .. import _cabi as C
 from .. import functional as F
 from .. import multi_tensor as mt
-from ..dlrm.engine import GradScalerState
+from ..utils.amp import GradScalerState
 from ..utils.buckets import GradBuckets
 from . import ops
 from .model import UPSAMPLE_KERNEL, UPSAMPLE_STRIDE, FlatViews, WaveGlow, flow_channels

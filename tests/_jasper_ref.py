@@ -5,7 +5,7 @@ whole-network tests run on.
 
 forward64(state, cfg, feats, dtype=None, emulate=False, lead=16)
     feats: a list of log-mel [n_feat, frames] tensors.  dtype: the 16-bit type whose rounding is applied to the WEIGHTS first (the
-    weights as the recognizer holds them; the BatchNorm coefficients are the fp32 fold of convnets.infer.fold_bn); None: the weights
+    weights as the recognizer holds them; the BatchNorm coefficients are the fp32 fold of utils.state.fold_bn); None: the weights
     as they are and the BatchNorm fold in float64 (the reference's module under .double()).  emulate: also round every value to
     `dtype` where the recognizer rounds -- the packed features, every sub-block's output, every link of the residual chain.
     lead: zero frames in front of the normalised features.  -> (list of float64 log-probs [out_len, n_classes], max |activation|).
@@ -22,7 +22,7 @@ import collections
 
 import torch
 
-from deeplearningexamples_amd.convnets.infer import fold_bn
+from deeplearningexamples_amd.utils.state import fold_bn
 from deeplearningexamples_amd.jasper.model import BN_EPS, check_config, state_shapes
 from tests._quartznet_ref import FEATURES, LABELS, clone_state, ctc_collapse, seeded_features      # noqa: F401
 

@@ -4,7 +4,7 @@ result for an utterance does not depend on its batch), and the seeded weights th
 
 forward64(state, cfg, feats, dtype=None, emulate=False)
     feats: a list of log-mel [n_feat, frames] tensors.  dtype: the 16-bit type whose rounding is applied to the WEIGHTS first (the
-    weights as the recognizer holds them; the BatchNorm coefficients are the fp32 fold of convnets.infer.fold_bn); None: the weights
+    weights as the recognizer holds them; the BatchNorm coefficients are the fp32 fold of utils.state.fold_bn); None: the weights
     as they are and the BatchNorm fold in float64 (the reference's module under .double()).  emulate: also round every value to `dtype` where the recognizer rounds -- the packed features, d, each unit's
     output, each residual branch's output.  -> (list of float64 log-probs [out_len, n_classes], max |activation|).
 fill_state(cfg, seed, calibrated)
@@ -19,7 +19,7 @@ import itertools
 
 import torch
 
-from deeplearningexamples_amd.convnets.infer import fold_bn
+from deeplearningexamples_amd.utils.state import fold_bn
 from deeplearningexamples_amd.quartznet.model import BN_EPS, check_config, state_shapes
 
 F64 = torch.float64

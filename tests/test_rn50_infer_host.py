@@ -11,7 +11,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import _ref_import as R  # noqa: E402
 
 from deeplearningexamples_amd.convnets import checkpoint2model, classify  # noqa: E402
-from deeplearningexamples_amd.convnets.infer import ResNet50Classifier, fold_bn, state_from_checkpoint  # noqa: E402
+from deeplearningexamples_amd.convnets.infer import ResNet50Classifier, state_from_checkpoint  # noqa: E402
+from deeplearningexamples_amd.utils.state import fold_bn  # noqa: E402
 
 needs_ref = pytest.mark.skipif(not R.have_reference(), reason="reference tree not mounted")
 

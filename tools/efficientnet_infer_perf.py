@@ -70,7 +70,7 @@ def timed(legs, reps):
 def layer_worker(args):
     import torch
     from deeplearningexamples_amd import functional as F
-    from deeplearningexamples_amd.convnets.infer import fold_bn
+    from deeplearningexamples_amd.utils.state import fold_bn
     dev = torch.device("cuda", 0)
     dtype = torch.bfloat16 if args.amp_dtype == "bf16" else torch.float16
     tf = torch.nn.functional

@@ -193,7 +193,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: this tool measures on the MI355X only")
     if args.config:
-        from deeplearningexamples_amd.jasper.model import load_config
+        from deeplearningexamples_amd.utils.state import load_config
         config = json.loads(json.dumps(load_config(args.config)))            # (the YAML's anchors share block dicts)
     else:
         config = config_10x5dr()

@@ -161,7 +161,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: this tool measures on the MI355X only")
     if args.config:
-        from deeplearningexamples_amd.quartznet.model import load_config
+        from deeplearningexamples_amd.utils.state import load_config
         config = load_config(args.config)
     else:
         config = config_15x5()
