@@ -153,6 +153,10 @@ __device__ __forceinline__ ushort8_t pack8(const float* v) {
   }
   return __builtin_bit_cast(ushort8_t, o);
 }
+// Keep bit of a ReLU output (>= 0) stored as the 16-bit pattern h: "the STORED value is positive", what a backward pass that reads
+// y > 0 from the activation would see (as gemm8_kernel.h takes it).  An fp32 value in (0, 2^-25] rounds to an fp16 zero, one below
+// 2^-134 to a bf16 zero: the fp32 sign test would keep a gradient that the stored activation has lost.
+__device__ __forceinline__ unsigned keep_bit16(unsigned short h) { return h != 0 ? 1u : 0u; }
 // 8 packed 16-bit values -> 8 fp32 (bf16: one shift / mask per element)
 template <int DT>
 __device__ __forceinline__ void unpack8(ushort8_t u8, float* v) {

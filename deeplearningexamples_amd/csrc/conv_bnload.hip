@@ -128,16 +128,16 @@ __global__ __launch_bounds__(NW * 64) void conv_bnload_kernel(BnlArgs p) {
           for (int k = 0; k < 8; ++k) rf[k] = rf[k] * sr[k] + hr[k];
           unpack8<DT>(pack8<DT>(rf), rf);                               // (the rounding point of the stand-alone branch output)
         }
-        unsigned bits = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           float v = xf[k] * sc[k] + sh[k];
           if (RES) v += rf[k];
-          v = v > 0.f ? v : 0.f;
-          of[k] = v;
-          bits |= (v > 0.f ? 1u : 0u) << k;
+          of[k] = v > 0.f ? v : 0.f;
         }
         fa[ks] = pack8<DT>(of);
+        unsigned bits = 0;                                              // keep bits of the STORED y (keep_bit16)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) bits |= keep_bit16(fa[ks][k]) << k;
         if (writer && live) {
           *(ushort8_t*)(p.Y + o + ks * 32) = fa[ks];
           p.bits[(o + ks * 32) >> 3] = (unsigned char)bits;

@@ -502,11 +502,12 @@ __global__ __launch_bounds__(256) void bn_apply_pf_kernel(const unsigned short* 
       if constexpr (ACT >= 1) v = v > 0.f ? v : 0.f;
       of[k] = v;
     }
-    ((ushort8_t*)y)[i] = pack8<DT>(of);
+    const ushort8_t ov = pack8<DT>(of);
+    ((ushort8_t*)y)[i] = ov;
     if constexpr (ACT == 2) {
-      unsigned bits = 0;
+      unsigned bits = 0;                                  // keep bits of the STORED y (keep_bit16)
 #pragma unroll
-      for (int k = 0; k < 8; ++k) bits |= (of[k] > 0.f ? 1u : 0u) << k;
+      for (int k = 0; k < 8; ++k) bits |= keep_bit16(ov[k]) << k;
       mask_out[i] = (unsigned char)bits;
     }
   };
@@ -581,16 +582,17 @@ __global__ __launch_bounds__(256) void bn_apply2_pf_kernel(const unsigned short*
 #pragma unroll
     for (int k = 0; k < 8; ++k) rf[k] = rf[k] * scr[k] + shr[k];
     unpack8<DT>(pack8<DT>(rf), rf);                       // (the rounding point of the stand-alone branch output)
-    unsigned bits = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float v = xf[k] * sc[k] + sh[k];
       v += rf[k];
-      v = v > 0.f ? v : 0.f;
-      of[k] = v;
-      bits |= (v > 0.f ? 1u : 0u) << k;
+      of[k] = v > 0.f ? v : 0.f;
     }
-    ((ushort8_t*)y)[i] = pack8<DT>(of);
+    const ushort8_t ov = pack8<DT>(of);
+    ((ushort8_t*)y)[i] = ov;
+    unsigned bits = 0;                                    // keep bits of the STORED y (keep_bit16)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) bits |= keep_bit16(ov[k]) << k;
     mask_out[i] = (unsigned char)bits;
   };
   long long i = first;
@@ -1334,8 +1336,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_k3s2_kernel(const unsigne
         for (int k = 0; k < 8; ++k) {
           float f = xf[k] * sc[k] + sh[k];
           f = f > 0.f ? f : 0.f;
-          bits |= (f > 0.f ? 1u : 0u) << k;
-          const float fr = up16<DT>(dn16<DT>(f));              // the value the stand-alone apply pass stores
+          const unsigned short fh = dn16<DT>(f);
+          const float fr = up16<DT>(fh);                       // the value the stand-alone apply pass stores
+          bits |= keep_bit16(fh) << k;                  // ... and its keep bit
           if (valid && (fr > best[k] || fr != fr)) { best[k] = fr; bi[k] = (unsigned)(r * 3 + s2); }
         }
         if (r >= 1 && s2 >= 1 && h < H && w < W) mask[(((unsigned)n * H + h) * W + w) * C8 + c8] = (unsigned char)bits;
