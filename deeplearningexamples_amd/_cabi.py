@@ -271,6 +271,10 @@ _SIGS = {
     "dle_tft_lstm_fwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dle_tft_attention_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "dle_ncf_score_supported": (c_int, [c_int] * 5),
+    "dle_ncf_score_fwd": (c_int, [c_void_p] * 4 + [c_i64, c_i64] + [c_void_p] * 10 + [c_int] + [c_void_p] * 4 + [c_int, c_i64] +
+                          [c_int] * 7 + [c_void_p]),
+    "dle_ncf_rank_fwd": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -15,28 +15,12 @@ import torch
 
 from .. import _cabi as C
 from .. import functional as F
+from ..utils.frontend import CAST_CHUNK_ROWS, cast_table_chunked  # noqa: F401  (shared with the other table front ends)
 from .model import DistributedDlrm
-
-CAST_CHUNK_ROWS = 1 << 20
 
 # Batch sizes at which the fused launch measured slower than the unfused pair (tools/dlrm_infer_perf.py): routed to the
 # pair.  Empty: the fused route did not lose at any measured size.
 UNFUSED_BATCH_SIZES = frozenset()
-
-
-def cast_table_chunked(weight, dtype, chunk_rows=CAST_CHUNK_ROWS):
-    """16-bit copy of a [rows, dim] fp32 table, cast chunk_rows rows at a time straight into the copy (round to nearest even, once
-    per element): nothing table-sized besides the copy itself is ever allocated."""
-    if weight.dim() != 2 or chunk_rows < 1:
-        raise ValueError("cast_table_chunked: a 2-D table and a positive chunk")
-    out = torch.empty(weight.shape, dtype=dtype, device=weight.device)
-    for r0 in range(0, weight.shape[0], chunk_rows):
-        src, dst = weight[r0:r0 + chunk_rows], out[r0:r0 + chunk_rows]
-        if weight.is_cuda:
-            F.cast_rows(src, dtype, out=dst)
-        else:
-            dst.copy_(src)
-    return out
 
 
 class DlrmPredictor:

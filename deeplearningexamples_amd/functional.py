@@ -2661,3 +2661,89 @@ def tft_attention_fwd(qkv, wo, B, T, encoder_length, heads=4, want_probs=False):
     C.call("dle_tft_attention_fwd", C.ptr(qkv), qkv.stride(0) if B * T > 1 else 288, C.ptr(wo), C.ptr(out), C.ptr(probs), B, T, enc, heads, 32,
            C.dt(qkv), C.stream())
     return (out, probs) if want_probs else out
+
+
+# ------------------------------------------------------------------ NCF (csrc/ncf.hip)
+def ncf_score_supported(factors, layers):
+    """Whether dle_ncf_score_fwd is built for this architecture (host only, no launch): --factors 64 --layers 256 256 128 64."""
+    layers = [int(n) for n in layers]
+    return len(layers) == 4 and bool(C.lib().dle_ncf_score_supported(int(factors), *layers))
+
+
+def ncf_score_fwd(mf_user, mf_item, mlp_user, mlp_item, weights, biases, wf, bf, user, item, label=None, want_prob=False,
+                  max_workgroups=0, logit_out=None, prob_out=None):
+    """NeuMF.forward of `user` / `item` (int32 or int64 [B]) in one persistent launch.  Tables and weights = (W1, W2, W3) 16-bit,
+    biases = (b1, b2, b3), wf [factors + l3] and bf [1] fp32.  Returns (logit fp32 [B], prob fp32 [B] or None, loss partials fp32
+    or None): with label (fp32 [B]) the partials hold one binary cross-entropy sum per workgroup, zeros behind the grid; their
+    sum is the batch's loss sum.  A sample with an index outside its table gets NaN and adds nothing to the loss."""
+    name = "ncf_score_fwd"
+    tables = (mf_user, mf_item, mlp_user, mlp_item)
+    C.require_cuda(*tables, *weights, *biases, wf, bf, user, item, label, logit_out, prob_out)
+    dtype = mf_user.dtype
+    if dtype not in _FP16:
+        raise ValueError("%s: 16-bit tables and weights only (got %s)" % (name, dtype))
+    for t in tables + tuple(weights):
+        if t.dtype != dtype or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError("%s: tables and weights must be contiguous 2-D tensors of one 16-bit type" % name)
+    if len(weights) != 3 or len(biases) != 3:
+        raise ValueError("%s: three MLP layers (got %d weights, %d biases)" % (name, len(weights), len(biases)))
+    factors, l0 = mf_user.shape[1], 2 * mlp_user.shape[1]
+    l1, l2, l3 = (w.shape[0] for w in weights)
+    if mf_item.shape[1] != factors or mlp_item.shape[1] * 2 != l0 or mf_user.shape[0] != mlp_user.shape[0] or \
+            mf_item.shape[0] != mlp_item.shape[0]:
+        raise ValueError("%s: the user tables and the item tables must agree in rows, the GMF and MLP pairs in width" % name)
+    if [w.shape[1] for w in weights] != [l0, l1, l2]:
+        raise ValueError("%s: weight shapes do not chain: %s" % (name, [tuple(w.shape) for w in weights]))
+    for b, n in zip(tuple(biases) + (wf, bf), (l1, l2, l3, factors + l3, 1)):
+        if b.dtype != torch.float32 or b.numel() != n or not b.is_contiguous():
+            raise ValueError("%s: biases and the final layer are contiguous fp32 tensors of %d elements" % (name, n))
+    if user.dtype != item.dtype or user.dtype not in (torch.int32, torch.int64) or user.dim() != 1 or user.shape != item.shape or \
+            not user.is_contiguous() or not item.is_contiguous():
+        raise ValueError("%s: user and item must be contiguous int32 or int64 vectors of one length" % name)
+    B, dev = user.numel(), mf_user.device
+    if label is not None and (label.dtype != torch.float32 or label.numel() != B or not label.is_contiguous()):
+        raise ValueError("%s: label must be a contiguous fp32 vector of the batch's length" % name)
+    if max_workgroups < 0:
+        raise ValueError("%s: max_workgroups must be 0 (the device's CU count) or positive" % name)
+    logit = torch.empty(B, dtype=torch.float32, device=dev) if logit_out is None else logit_out
+    prob = (torch.empty(B, dtype=torch.float32, device=dev) if prob_out is None else prob_out) if want_prob or prob_out is not None else None
+    for t in (logit, prob):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError("%s: outputs are contiguous fp32 vectors of the batch's length" % name)
+    partials = None
+    if label is not None:
+        n = int(max_workgroups) or torch.cuda.get_device_properties(dev).multi_processor_count
+        partials = torch.empty(n, dtype=torch.float32, device=dev)
+    if B == 0:                                        # nothing to launch (and no pointer to hand over)
+        return logit, prob, (partials.zero_() if partials is not None else None)
+    C.annotate(flops=2.0 * B * (l0 * l1 + l1 * l2 + l2 * l3 + factors + l3), bytes=float(B) * (2 * (factors + l0 // 2) * 2 + 4),
+               tag="ncf_score %d" % B)
+    C.call("dle_ncf_score_fwd", C.ptr(mf_user), C.ptr(mf_item), C.ptr(mlp_user), C.ptr(mlp_item), mf_user.shape[0], mf_item.shape[0],
+           C.ptr(weights[0]), C.ptr(biases[0]), C.ptr(weights[1]), C.ptr(biases[1]), C.ptr(weights[2]), C.ptr(biases[2]), C.ptr(wf),
+           C.ptr(bf), C.ptr(user), C.ptr(item), 64 if user.dtype == torch.int64 else 32, C.ptr(label), C.ptr(logit), C.ptr(prob),
+           C.ptr(partials), partials.numel() if partials is not None else 0, B, factors, l0, l1, l2, l3, int(max_workgroups),
+           C.dt(dtype), C.stream())
+    return logit, prob, partials
+
+
+def ncf_rank_fwd(rating, label, ignore, samples_per_series, k):
+    """hits (int32) and dcg (fp32) per series of `samples_per_series` elements by the stated rank rule of dle_ncf_rank_fwd:
+    rating, label fp32 [n_series * S], ignore bool / uint8 of that length or None."""
+    name = "ncf_rank_fwd"
+    C.require_cuda(rating, label, ignore)
+    S, k = int(samples_per_series), int(k)
+    if rating.dtype != torch.float32 or label.dtype != torch.float32 or not rating.is_contiguous() or not label.is_contiguous() or \
+            rating.numel() != label.numel():
+        raise ValueError("%s: rating and label must be contiguous fp32 tensors of one length" % name)
+    if S < 1 or rating.numel() % S:
+        raise ValueError("%s: %d elements are not whole series of %d" % (name, rating.numel(), S))
+    if ignore is not None:
+        if ignore.dtype == torch.bool:
+            ignore = ignore.view(torch.uint8)
+        if ignore.dtype != torch.uint8 or ignore.numel() != rating.numel() or not ignore.is_contiguous():
+            raise ValueError("%s: ignore must be a contiguous bool or uint8 tensor of the ratings' length" % name)
+    n = rating.numel() // S
+    hits = torch.empty(n, dtype=torch.int32, device=rating.device)
+    dcg = torch.empty(n, dtype=torch.float32, device=rating.device)
+    C.call("dle_ncf_rank_fwd", C.ptr(rating), C.ptr(label), C.ptr(ignore), C.ptr(hits), C.ptr(dcg), n, S, k, C.stream())
+    return hits, dcg

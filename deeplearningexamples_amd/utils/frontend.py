@@ -5,7 +5,10 @@ rejected in; require_16bit comes first everywhere and touches no device, so a ho
 import torch
 
 from .. import _cabi as C
+from .. import functional as F
 from .graph import GraphedStep
+
+CAST_CHUNK_ROWS = 1 << 20
 
 
 def require_16bit(dtype, who):
@@ -39,3 +42,18 @@ class GraphCache(dict):
         if g is None:
             g = self[key] = GraphedStep(fn, warmup_steps=2)
         return g(*tensors)
+
+
+def cast_table_chunked(weight, dtype, chunk_rows=CAST_CHUNK_ROWS):
+    """16-bit copy of a [rows, dim] fp32 table, cast chunk_rows rows at a time straight into the copy (round to nearest even, once
+    per element): nothing table-sized besides the copy itself is ever allocated."""
+    if weight.dim() != 2 or chunk_rows < 1:
+        raise ValueError("cast_table_chunked: a 2-D table and a positive chunk")
+    out = torch.empty(weight.shape, dtype=dtype, device=weight.device)
+    for r0 in range(0, weight.shape[0], chunk_rows):
+        src, dst = weight[r0:r0 + chunk_rows], out[r0:r0 + chunk_rows]
+        if weight.is_cuda:
+            F.cast_rows(src, dtype, out=dst)
+        else:
+            dst.copy_(src)
+    return out

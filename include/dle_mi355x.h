@@ -1167,6 +1167,35 @@ int dle_tft_lstm_fwd(const float* xproj, int64_t xp_batch_stride, int64_t xp_ste
 int dle_tft_attention_fwd(const void* qkv, int64_t ld, const void* wo, void* out, float* probs, int B, int T, int encoder_length,
                           int heads, int d_head, int dtype, hipStream_t stream);
 
+/* ---- Neural Collaborative Filtering inference and evaluation (csrc/ncf.hip; reference PyTorch/Recommendation/NCF) -----------
+ * dle_ncf_score_fwd: NeuMF.forward (neumf.py:80-98) with the sigmoid of inference.py:90 and the binary cross-entropy of
+ *   val_epoch (ncf.py:141-144), one persistent launch:
+ *     logit[b] = wf[:F] . (mf_user[user[b]] * mf_item[item[b]]) + wf[F:] . relu(W3 h2 + b3) + bf,
+ *     h1 = round16(relu(W1 [mlp_user[user[b]] | mlp_item[item[b]]] + b1)),  h2 = round16(relu(W2 h1 + b2)).
+ *   Tables mf_* [n, factors], mlp_* [n, l0 / 2] and W1 [l1][l0], W2 [l2][l1], W3 [l3][l2] are 16-bit (DLE_F16 / DLE_BF16), row-major,
+ *   16-byte aligned; b1..b3, wf [factors + l3] and bf [1] are fp32.  Rounding contract: h1 and h2 are rounded to 16 bits once, on
+ *   their way into the next MFMA operand; the GMF product, the third layer's output, the dot product, the sigmoid and the loss
+ *   are fp32 and never rounded.  user / item: `batch` indices of index_bits = 32 or 64.  A sample whose user or item index is
+ *   outside [0, n_users) / [0, n_items) reads nothing from the tables, gets a NaN logit and probability and adds nothing to the
+ *   loss.  prob (fp32 [batch] or NULL) = sigmoid(logit).  label (fp32 [batch]) and loss_partials (fp32 [n_partials]) go together
+ *   or are both NULL: workgroup g writes the sum of -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) over its samples to
+ *   loss_partials[g] (computed from the fp32 logit), the slots behind the grid are zeroed, no atomics: the caller folds them.
+ *   The grid is min(ceil(batch / 64), max_workgroups or the device's CU count when 0, n_partials when the loss is asked for).
+ *   Envelope (dle_ncf_score_supported, host only, 1 / 0): factors 64, layers 256 256 128 64 -- ncf.py's defaults (:69-73).
+ * dle_ncf_rank_fwd: the ranking tail of val_epoch (ncf.py:150-162: the -1 over the mask, topk, gather, nonzero) per series of S
+ *   elements, without a sort and without topk's tie order: r_j = -1 where ignore_j (one byte per element, or NULL) is set, else
+ *   rating_j; rank_j = #{i : r_i > r_j or (r_i == r_j and i < j)}; NaN ranks below everything, NaNs among themselves by index.
+ *   hits[s] = #{j : label_j == 1 and rank_j < k}, dcg[s] = sum over those j of log 2 / log(rank_j + 2).  1 <= k <= S <= 4096.
+ * Both: -1 and a message, nothing launched, on a bad argument.                                                                 */
+int dle_ncf_score_supported(int factors, int l0, int l1, int l2, int l3);
+int dle_ncf_score_fwd(const void* mf_user, const void* mf_item, const void* mlp_user, const void* mlp_item, int64_t n_users,
+                      int64_t n_items, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
+                      const float* b3, const float* wf, const float* bf, const void* user, const void* item, int index_bits,
+                      const float* label, float* logit, float* prob, float* loss_partials, int n_partials, int64_t batch,
+                      int factors, int l0, int l1, int l2, int l3, int max_workgroups, int dtype, hipStream_t stream);
+int dle_ncf_rank_fwd(const float* rating, const float* label, const uint8_t* ignore, int32_t* hits, float* dcg, int64_t n_series,
+                     int S, int k, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
