@@ -275,6 +275,13 @@ _SIGS = {
     "dle_ncf_score_fwd": (c_int, [c_void_p] * 4 + [c_i64, c_i64] + [c_void_p] * 10 + [c_int] + [c_void_p] * 4 + [c_int, c_i64] +
                           [c_int] * 7 + [c_void_p]),
     "dle_ncf_rank_fwd": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_void_p]),
+    "dle_conv3d_in_bands": (c_int, [c_int] * 4),
+    "dle_conv3d_in_fwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p] + [c_int] * 10 +
+                          [c_void_p]),
+    "dle_instnorm_fold": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "dle_upsample3d_x2_bands": (c_int, [c_int] * 3),
+    "dle_upsample3d_x2_fwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "dle_nnunet_head_blend_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),
 }
 
 _lib = None

@@ -2747,3 +2747,121 @@ def ncf_rank_fwd(rating, label, ignore, samples_per_series, k):
     dcg = torch.empty(n, dtype=torch.float32, device=rating.device)
     C.call("dle_ncf_rank_fwd", C.ptr(rating), C.ptr(label), C.ptr(ignore), C.ptr(hits), C.ptr(dcg), n, S, k, C.stream())
     return hits, dcg
+
+
+# ------------------------------------------------------------------ nnU-Net (csrc/nnunet.hip)
+def _nu_volume(t, name):
+    """(N, D, H, W, ld) of a contiguous channels-last 16-bit volume [N, D, H, W, ld]."""
+    if t.dim() != 5 or not t.is_contiguous() or t.dtype not in _FP16:
+        raise ValueError("%s: volumes are contiguous 16-bit [N, D, H, W, ld] tensors (got %s %s)" % (name, t.dtype, tuple(t.shape)))
+    return tuple(int(s) for s in t.shape)
+
+
+def conv3d_in_bands(D, H, W, stride):
+    """Statistic bands per sample of conv3d_in_fwd's output for a [D, H, W] input (host only)."""
+    g = int(C.lib().dle_conv3d_in_bands(int(D), int(H), int(W), int(stride)))
+    if g < 1:
+        raise ValueError("conv3d_in_bands: extents >= 1 and stride 1 or 2 (got %s, stride %s)" % ((D, H, W), stride))
+    return g
+
+
+def conv3d_in_fwd(x, weight, y, C_in=None, x_off=0, y_off=0, scale=None, shift=None, stride=1, relu_in=False, relu_out=True, part=None):
+    """3x3x3 pad-1 convolution of channels [x_off, x_off + C_in) of x [N, D, H, W, ldx] into channels [y_off, y_off + Ko) of
+    y [N, P, Q, R, ldy], with a = round16(relu_in?(scale[n, c] * x + shift[n, c])) applied on the operand load (scale None: a = x).
+    weight [Ko, 3, 3, 3, C_in] 16-bit; scale, shift fp32 [N, C_in]; part None or fp32 [N, G, Ko, 3] receives (count, sum, M2) of the
+    stored output per band.  Returns y."""
+    name = "conv3d_in_fwd"
+    C.require_cuda(x, weight, y, scale, shift, part)
+    N, D, H, W, ldx = _nu_volume(x, name)
+    Ny, P, Q, R, ldy = _nu_volume(y, name)
+    if weight.dim() != 5 or tuple(weight.shape[1:4]) != (3, 3, 3) or weight.dtype != x.dtype or y.dtype != x.dtype or not weight.is_contiguous():
+        raise ValueError("%s: weight is a contiguous [Ko, 3, 3, 3, C] tensor of the volumes' type (got %s %s)" % (name, weight.dtype, tuple(weight.shape)))
+    Ko, Cw = int(weight.shape[0]), int(weight.shape[4])
+    C_in = Cw if C_in is None else int(C_in)
+    stride = int(stride)
+    if C_in != Cw:
+        raise ValueError("%s: the weight has %d input channels, the call names %d" % (name, Cw, C_in))
+    if stride not in (1, 2) or (Ny, P, Q, R) != (N, (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError("%s: output %s does not belong to input %s at stride %s" % (name, (Ny, P, Q, R), (N, D, H, W), stride))
+    if (scale is None) != (shift is None):
+        raise ValueError("%s: scale and shift go together" % name)
+    for t in (scale, shift):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (N, C_in) or not t.is_contiguous()):
+            raise ValueError("%s: scale and shift are contiguous fp32 [N, C] = [%d, %d] tensors" % (name, N, C_in))
+    if part is not None:
+        G = conv3d_in_bands(D, H, W, stride)
+        if part.dtype != torch.float32 or tuple(part.shape) != (N, G, Ko, 3) or not part.is_contiguous():
+            raise ValueError("%s: part is a contiguous fp32 [N, G, Ko, 3] = [%d, %d, %d, 3] tensor" % (name, N, G, Ko))
+    C.annotate(flops=2.0 * N * P * Q * R * 27 * C_in * Ko, bytes=2.0 * (N * D * H * W * C_in + N * P * Q * R * Ko + 27 * C_in * Ko),
+               tag="conv3d_in %dx%dx%dx%d c%d k%d s%d" % (N, D, H, W, C_in, Ko, stride))
+    C.call("dle_conv3d_in_fwd", C.ptr(x), ldx, int(x_off), C.ptr(scale), C.ptr(shift), C.ptr(weight), C.ptr(y), ldy, int(y_off), C.ptr(part),
+           N, D, H, W, C_in, Ko, stride, int(bool(relu_in)), int(bool(relu_out)), C.dt(x), C.stream())
+    return y
+
+
+def instnorm_fold(part, gamma, beta, eps, scale, shift, out_off=0):
+    """part fp32 [N, G, C, 3] -> scale = gamma / sqrt(var + eps), shift = beta - mean * scale (biased variance, Chan's merge in band
+    order) into channels [out_off, out_off + C) of scale, shift fp32 [N, ld]."""
+    name = "instnorm_fold"
+    C.require_cuda(part, gamma, beta, scale, shift)
+    if part.dtype != torch.float32 or part.dim() != 4 or part.shape[3] != 3 or not part.is_contiguous():
+        raise ValueError("%s: part is a contiguous fp32 [N, G, C, 3] tensor" % name)
+    N, G, Cn = (int(s) for s in part.shape[:3])
+    for t in (gamma, beta):
+        if t.dtype != torch.float32 or t.numel() != Cn or not t.is_contiguous():
+            raise ValueError("%s: gamma and beta are contiguous fp32 vectors of %d elements" % (name, Cn))
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != N or not t.is_contiguous() or t.shape != scale.shape:
+            raise ValueError("%s: scale and shift are contiguous fp32 [N, ld] tensors of one shape" % name)
+    C.call("dle_instnorm_fold", C.ptr(part), G, Cn, C.ptr(gamma), C.ptr(beta), float(eps), C.ptr(scale), C.ptr(shift), int(scale.shape[1]),
+           int(out_off), N, C.stream())
+    return scale, shift
+
+
+def upsample3d_x2_bands(D, H, W):
+    g = int(C.lib().dle_upsample3d_x2_bands(int(D), int(H), int(W)))
+    if g < 1:
+        raise ValueError("upsample3d_x2_bands: extents >= 1 (got %s)" % ((D, H, W),))
+    return g
+
+
+def upsample3d_x2_fwd(x, y, channels=None, x_off=0, y_off=0, part=None):
+    """Trilinear x2 upsample (align_corners=True) of channels [x_off, x_off + channels) of x [N, D, H, W, ldx] into channels
+    [y_off, ...) of y [N, 2D, 2H, 2W, ldy]; part None or fp32 [N, G, channels, 3].  Returns y."""
+    name = "upsample3d_x2_fwd"
+    C.require_cuda(x, y, part)
+    N, D, H, W, ldx = _nu_volume(x, name)
+    Ny, P, Q, R, ldy = _nu_volume(y, name)
+    Cn = ldx if channels is None else int(channels)
+    if (Ny, P, Q, R) != (N, 2 * D, 2 * H, 2 * W) or y.dtype != x.dtype:
+        raise ValueError("%s: output %s is not twice the input %s" % (name, (Ny, P, Q, R), (N, D, H, W)))
+    if part is not None:
+        G = upsample3d_x2_bands(D, H, W)
+        if part.dtype != torch.float32 or tuple(part.shape) != (N, G, Cn, 3) or not part.is_contiguous():
+            raise ValueError("%s: part is a contiguous fp32 [N, G, C, 3] = [%d, %d, %d, 3] tensor" % (name, N, G, Cn))
+    C.annotate(bytes=2.0 * N * D * H * W * Cn * 9, tag="upsample3d %dx%dx%dx%d c%d" % (N, D, H, W, Cn))
+    C.call("dle_upsample3d_x2_fwd", C.ptr(x), ldx, int(x_off), C.ptr(y), ldy, int(y_off), C.ptr(part), N, D, H, W, Cn, C.dt(x), C.stream())
+    return y
+
+
+def nnunet_head_blend_fwd(x, weight, bias, imp, out, origin):
+    """out[k, d0 + d, h0 + h, w0 + w] += imp[d, h, w] * (bias[k] + sum_c weight[k, c] * x[d, h, w, c]) for ONE window x [Dp, Hp, Wp, ld]
+    (16-bit, channels last); weight 16-bit [K, C], bias fp32 [K], imp fp32 [Dp, Hp, Wp], out fp32 [K, Dv, Hv, Wv], origin (d0, h0, w0)."""
+    name = "nnunet_head_blend_fwd"
+    C.require_cuda(x, weight, bias, imp, out)
+    if x.dim() != 4 or x.dtype not in _FP16 or not x.is_contiguous():
+        raise ValueError("%s: the window is a contiguous 16-bit [Dp, Hp, Wp, ld] tensor" % name)
+    Dp, Hp, Wp, ld = (int(s) for s in x.shape)
+    if weight.dim() != 2 or weight.dtype != x.dtype or not weight.is_contiguous():
+        raise ValueError("%s: weight is a contiguous [K, C] tensor of the window's type" % name)
+    K, Cn = (int(s) for s in weight.shape)
+    if bias.dtype != torch.float32 or bias.numel() != K or not bias.is_contiguous():
+        raise ValueError("%s: bias is a contiguous fp32 vector of %d elements" % (name, K))
+    if imp.dtype != torch.float32 or tuple(imp.shape) != (Dp, Hp, Wp) or not imp.is_contiguous():
+        raise ValueError("%s: imp is a contiguous fp32 [%d, %d, %d] tensor" % (name, Dp, Hp, Wp))
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != K or not out.is_contiguous():
+        raise ValueError("%s: out is a contiguous fp32 [K, Dv, Hv, Wv] tensor" % name)
+    d0, h0, w0 = (int(v) for v in origin)
+    C.call("dle_nnunet_head_blend_fwd", C.ptr(x), ld, C.ptr(weight), C.ptr(bias), C.ptr(imp), C.ptr(out), K, Cn, Dp, Hp, Wp, int(out.shape[1]),
+           int(out.shape[2]), int(out.shape[3]), d0, h0, w0, C.dt(x), C.stream())
+    return out

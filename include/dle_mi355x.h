@@ -1196,6 +1196,43 @@ int dle_ncf_score_fwd(const void* mf_user, const void* mf_item, const void* mlp_
 int dle_ncf_rank_fwd(const float* rating, const float* label, const uint8_t* ignore, int32_t* hits, float* dcg, int64_t n_series,
                      int S, int k, hipStream_t stream);
 
+/* ---- nnU-Net BraTS22 UNet3D inference (csrc/nnunet.hip; reference PyTorch/Segmentation/nnUNet/nnunet/brats22_model.py) ------
+ * Volumes are channels-last: x [N, D, H, W, ldx], y [N, P, Q, R, ldy], 16-bit (DLE_F16 / DLE_BF16); a tensor is addressed as
+ * (base, leading dimension, channel offset), so a layer reads and writes a channel slice of a wider buffer (the concat buffer of
+ * UpsampleBlock.forward, :119-121, is never copied into).  Statistic partials: fp32 [N][G][channels][3] = (count, sum, M2) of the
+ * STORED 16-bit values over the output voxels of band g of sample n, written once by one workgroup in a fixed order, no atomics.
+ * dle_conv3d_in_fwd: ConvLayer.forward (:94-98: InstanceNorm3d, Conv3d 3x3x3 pad 1 bias=False, ReLU) and the two halves of
+ *   InputBlock.forward (:78-84), with the normalisation applied on the operand load:
+ *     a[n,d,h,w,c]  = inside the volume ? round16(relu_in ? max(.,0) : . of fmaf(scale[n,c], float(x), shift[n,c])) : 0
+ *                     (scale == shift == NULL: a = x)
+ *     y[n,p,q,r,ko] = round16(relu_out ? max(acc, 0) : acc),  acc = fp32 sum over the 27 taps and c of float(w) * float(a)
+ *   w [Ko][3][3][3][C]; scale, shift fp32 [N][C]; stride 1 or 2, P = (D - 1) / stride + 1; part NULL or [N][G][Ko][3] with
+ *   G = dle_conv3d_in_bands(D, H, W, stride) (host only).  Envelope: Ko % 64 == 0; C % 64 == 0 or C == 8; offsets and leading
+ *   dimensions multiples of 8; every pointer 16-byte aligned; every tensor below 2^31 elements.
+ * dle_instnorm_fold: nn.InstanceNorm3d(affine=True) in eval (:37) as a table: the bands of part [N][G][C][3] are merged by
+ *   Chan's formula in band order, scale = gamma / sqrt(M2 / count + eps), shift = beta - mean * scale (biased variance), written to
+ *   scale / shift [N][ld_out] at channel out_off.
+ * dle_upsample3d_x2_fwd: F.interpolate(scale_factor=2, mode="trilinear", align_corners=True) (:119): output index i of an axis
+ *   of extent E reads position i (E - 1) / (2 E - 1) (extent 1 copies); nested fp32 lerps along w, h, d, one rounding; part NULL
+ *   or [N][G][C][3], G = dle_upsample3d_x2_bands(D, H, W).  C % 8 == 0, C <= 2048.
+ * dle_nnunet_head_blend_fwd: OutputBlock.forward (:130-131, 1x1x1 convolution with bias) of ONE window x [Dp, Hp, Wp, ldx] fused
+ *   with the weighted accumulation of sliding_window_inference:
+ *     out[k, d0 + d, h0 + h, w0 + w] += imp[d,h,w] * (b[k] + sum_c float(w[k,c]) * float(x[d,h,w,c]))
+ *   out fp32 [K, Dv, Hv, Wv], imp fp32 [Dp, Hp, Wp], w 16-bit [K][C], b fp32 [K]; K <= 8, C % 8 == 0, C <= 512.  One window per
+ *   launch: overlapping windows are ordered by the stream, no atomics.
+ * All: no allocation, no synchronisation, graph capturable; -1 and a message, nothing launched, on a bad argument.              */
+int dle_conv3d_in_bands(int D, int H, int W, int stride);
+int dle_conv3d_in_fwd(const void* x, int64_t ldx, int64_t x_off, const float* scale, const float* shift, const void* w, void* y,
+                      int64_t ldy, int64_t y_off, float* part, int N, int D, int H, int W, int C, int Ko, int stride, int relu_in,
+                      int relu_out, int dtype, hipStream_t stream);
+int dle_instnorm_fold(const float* part, int G, int C, const float* gamma, const float* beta, float eps, float* scale, float* shift,
+                      int64_t ld_out, int64_t out_off, int N, hipStream_t stream);
+int dle_upsample3d_x2_bands(int D, int H, int W);
+int dle_upsample3d_x2_fwd(const void* x, int64_t ldx, int64_t x_off, void* y, int64_t ldy, int64_t y_off, float* part, int N, int D,
+                          int H, int W, int C, int dtype, hipStream_t stream);
+int dle_nnunet_head_blend_fwd(const void* x, int64_t ldx, const void* w, const float* b, const float* imp, float* out, int K, int C,
+                              int Dp, int Hp, int Wp, int Dv, int Hv, int Wv, int d0, int h0, int w0, int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
