@@ -275,6 +275,12 @@ _SIGS = {
     "dle_ncf_score_fwd": (c_int, [c_void_p] * 4 + [c_i64, c_i64] + [c_void_p] * 10 + [c_int] + [c_void_p] * 4 + [c_int, c_i64] +
                           [c_int] * 7 + [c_void_p]),
     "dle_ncf_rank_fwd": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_void_p]),
+    "dle_mf_squeeze_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "dle_mf_couple_fwd": (c_int, [c_void_p, c_i64] + [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
+    "dle_mf_bond_decide_fwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "dle_mf_atom_supported": (c_int, [c_int] * 10),
+    "dle_mf_atom_reverse_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p] + [c_int] * 12 +
+                                [c_void_p]),
     "dle_conv3d_in_bands": (c_int, [c_int] * 4),
     "dle_conv3d_in_fwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p] + [c_int] * 10 +
                           [c_void_p]),

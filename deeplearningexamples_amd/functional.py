@@ -2749,6 +2749,136 @@ def ncf_rank_fwd(rating, label, ignore, samples_per_series, k):
     return hits, dcg
 
 
+# ------------------------------------------------------------------ MoFlow (csrc/moflow.hip)
+def _mf_f32(name, t, numel, what):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError("%s: %s must be a contiguous fp32 tensor of %d elements" % (name, what, numel))
+    return t
+
+
+def _mf_rows(name, z, width, what):
+    """Row pitch of a 2-D fp32 [B, width] view with unit inner stride (a column slice of the latent vector)."""
+    if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != width or (width > 1 and z.stride(1) != 1):
+        raise ValueError("%s: %s must be fp32 [batch, %d] with unit inner stride" % (name, what, width))
+    return z.stride(0) if z.shape[0] > 1 else max(z.stride(0), width)
+
+
+def mf_squeeze_fwd(z_adj, n_node, fold, img_half, dtype, state=None, img=None):
+    """z_adj fp32 [B, 4 N N] (rows may be a slice of the latent vector) -> (state fp32 [B, P, C], 16-bit image [B, P, C/2] of half
+    img_half): Block._squeeze with channels innermost."""
+    name = "mf_squeeze_fwd"
+    C.require_cuda(z_adj, state, img)
+    if dtype not in _FP16:
+        raise ValueError("%s: the image is 16-bit (got %s)" % (name, dtype))
+    n, fold = int(n_node), int(fold)
+    if fold < 1 or n < 1 or n % fold:
+        raise ValueError("%s: n_node %d is not a multiple of the fold %d" % (name, n, fold))
+    ldz = _mf_rows(name, z_adj, 4 * n * n, "z_adj")
+    b, p, c = z_adj.shape[0], (n // fold) ** 2, 4 * fold * fold
+    state = torch.empty((b, p, c), dtype=torch.float32, device=z_adj.device) if state is None else _mf_f32(name, state, b * p * c, "state")
+    if img is None:
+        img = torch.empty((b, p, c // 2), dtype=dtype, device=z_adj.device)
+    elif img.dtype != dtype or not img.is_contiguous() or img.numel() != b * p * c // 2:
+        raise ValueError("%s: img must be a contiguous %s tensor of %d elements" % (name, dtype, b * p * c // 2))
+    if b:
+        C.call("dle_mf_squeeze_fwd", C.ptr(z_adj), ldz, C.ptr(state), C.ptr(img), b, n, fold, int(img_half), C.dt(dtype), C.stream())
+    return state, img
+
+
+def mf_couple_fwd(h2, w3, b3, scale, loc, state, positions, mask_swap, img_half=None, state_out=None, img=None):
+    """The third convolution of a bond coupling as the folded dense product + the rest of Flow.reverse (contract: dle_mi355x.h).
+    h2 16-bit [B, K], w3 16-bit [2 M, K], b3 fp32 [2 M], scale / loc fp32 [C], state fp32 [B, P, C] -> (new state, 16-bit image of
+    half img_half or None)."""
+    name = "mf_couple_fwd"
+    C.require_cuda(h2, w3, b3, scale, loc, state, state_out, img)
+    dtype = h2.dtype
+    if dtype not in _FP16 or w3.dtype != dtype:
+        raise ValueError("%s: 16-bit operands of one type (got %s, %s)" % (name, h2.dtype, w3.dtype))
+    if h2.dim() != 2 or w3.dim() != 2 or h2.stride(1) != 1 or not w3.is_contiguous() or w3.shape[1] != h2.shape[1] or w3.shape[0] % 2:
+        raise ValueError("%s: h2 [batch, K] and a contiguous w3 [2 M, K]" % name)
+    b, k, m, p = h2.shape[0], h2.shape[1], w3.shape[0] // 2, int(positions)
+    if p < 1 or m % p:
+        raise ValueError("%s: %d elements are not %d positions of whole channels" % (name, m, p))
+    ch = m // p
+    _mf_f32(name, b3, 2 * m, "b3"), _mf_f32(name, scale, 2 * ch, "scale"), _mf_f32(name, loc, 2 * ch, "loc")
+    _mf_f32(name, state, b * 2 * m, "state")
+    state_out = torch.empty_like(state) if state_out is None else _mf_f32(name, state_out, b * 2 * m, "state_out")
+    if img_half is not None and img is None:
+        img = torch.empty((b, p, ch), dtype=dtype, device=h2.device)
+    if img is not None and (img.dtype != dtype or not img.is_contiguous() or img.numel() != b * m or img_half is None):
+        raise ValueError("%s: img must be a contiguous %s tensor of %d elements, with img_half" % (name, dtype, b * m))
+    C.annotate(flops=4.0 * b * m * k, bytes=2.0 * (2 * m * k + b * k) + 16.0 * b * m + (2.0 * b * m if img is not None else 0.0),
+               tag="mf_couple %dx%dx%d" % (b, 2 * m, k))
+    C.call("dle_mf_couple_fwd", C.ptr(h2), h2.stride(0) if b > 1 else max(h2.stride(0), k), C.ptr(w3), C.ptr(b3), C.ptr(scale), C.ptr(loc),
+           C.ptr(state), C.ptr(state_out), C.ptr(img), b, p, ch, k, int(bool(mask_swap)), int(img_half or 0), C.dt(dtype), C.stream())
+    return state_out, img
+
+
+def mf_bond_decide_fwd(state, n_node, fold, unshift, want_adj=False, want_h=False, mask=None, code=None, adj01=None, h_adj=None):
+    """The tail of MoFlow.reverse's bond half by the stated rule of dle_mf_bond_decide_fwd: state fp32 [B, P, C] -> (mask uint8
+    [B, N, N], code uint8 [B, N, N], adj01 fp32 [B, 4, N, N] or None, h_adj fp32 [B, 4, N, N] or None)."""
+    name = "mf_bond_decide_fwd"
+    C.require_cuda(state, mask, code, adj01, h_adj)
+    n, fold = int(n_node), int(fold)
+    if fold < 1 or n < 1 or n % fold:
+        raise ValueError("%s: n_node %d is not a multiple of the fold %d" % (name, n, fold))
+    if state.dtype != torch.float32 or not state.is_contiguous() or state.numel() % (4 * n * n):
+        raise ValueError("%s: state must be a contiguous fp32 tensor of whole [4, %d, %d] samples" % (name, n, n))
+    b, dev = state.numel() // (4 * n * n), state.device
+    mask = torch.empty((b, n, n), dtype=torch.uint8, device=dev) if mask is None else mask
+    code = torch.empty((b, n, n), dtype=torch.uint8, device=dev) if code is None else code
+    for t in (mask, code):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != b * n * n:
+            raise ValueError("%s: mask and code are contiguous uint8 [batch, %d, %d]" % (name, n, n))
+    if want_adj and adj01 is None:
+        adj01 = torch.empty((b, 4, n, n), dtype=torch.float32, device=dev)
+    if want_h and h_adj is None:
+        h_adj = torch.empty((b, 4, n, n), dtype=torch.float32, device=dev)
+    for t in (adj01, h_adj):
+        if t is not None:
+            _mf_f32(name, t, b * 4 * n * n, "adj01 / h_adj")
+    if b:
+        C.call("dle_mf_bond_decide_fwd", C.ptr(state), C.ptr(mask), C.ptr(code), C.ptr(adj01), C.ptr(h_adj), b, n, fold, int(bool(unshift)),
+               C.stream())
+    return mask, code, adj01, h_adj
+
+
+def mf_atom_supported(n_node, n_type, hidden_gnn, hidden_lin, n_flow, n_block=1, mask_row_size=1):
+    """Whether dle_mf_atom_reverse_fwd is built for this atom flow (host only, no launch)."""
+    g, l = [int(v) for v in hidden_gnn], [int(v) for v in hidden_lin]
+    return bool(C.lib().dle_mf_atom_supported(int(n_node), int(n_type), int(n_block), len(g), g[0] if g else 0, len(l), l[0] if l else 0,
+                                              l[1] if len(l) > 1 else 0, int(n_flow), int(mask_row_size)))
+
+
+def mf_atom_reverse_fwd(z_x, mask, w16, p32, n_node, n_type, hidden_gnn, hidden_lin, row_stride, unshift, tile=32, max_workgroups=0,
+                        out=None):
+    """GlowOnGraph.reverse in one launch: z_x fp32 [B, N T] (rows may be a slice of the latent vector), mask uint8 [B, N, N] (the bits
+    of mf_bond_decide_fwd), w16 16-bit [n_flow, w_stride] / p32 fp32 [n_flow, p_stride] as moflow.model.pack_atom_flows lays them
+    out -> x fp32 [B, N, T]."""
+    name = "mf_atom_reverse_fwd"
+    C.require_cuda(z_x, mask, w16, p32, out)
+    n, t = int(n_node), int(n_type)
+    if w16.dtype not in _FP16 or w16.dim() != 2 or not w16.is_contiguous() or p32.dtype != torch.float32 or p32.dim() != 2 or \
+            not p32.is_contiguous() or p32.shape[0] != w16.shape[0]:
+        raise ValueError("%s: w16 [n_flow, pitch] 16-bit and p32 [n_flow, pitch] fp32, contiguous" % name)
+    ldz = _mf_rows(name, z_x, n * t, "z_x")
+    b = z_x.shape[0]
+    if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != b * n * n:
+        raise ValueError("%s: mask must be a contiguous uint8 [batch, %d, %d]" % (name, n, n))
+    if len(hidden_gnn) != 1 or len(hidden_lin) != 2:
+        raise ValueError("%s: built for one graph-convolution layer and two linear blocks (got %s, %s)" % (name, list(hidden_gnn), list(hidden_lin)))
+    if max_workgroups < 0:
+        raise ValueError("%s: max_workgroups must be 0 (the device's CU count) or positive" % name)
+    out = torch.empty((b, n, t), dtype=torch.float32, device=z_x.device) if out is None else _mf_f32(name, out, b * n * t, "out")
+    n_flow = w16.shape[0]
+    per = sum(a * c for a, c in zip([4 * t + 4, hidden_gnn[0], hidden_lin[0], hidden_lin[1]], [hidden_gnn[0], hidden_lin[0], hidden_lin[1], 2 * t]))
+    C.annotate(flops=2.0 * b * n_flow * per, bytes=float(w16.numel()) * 2 + b * (8.0 * n * t + n * n), tag="mf_atom %d" % b)
+    C.call("dle_mf_atom_reverse_fwd", C.ptr(z_x), ldz, C.ptr(mask), C.ptr(w16), w16.stride(0), C.ptr(p32), p32.stride(0), C.ptr(out), b, n, t,
+           int(hidden_gnn[0]), int(hidden_lin[0]), int(hidden_lin[1]), n_flow, int(row_stride), int(bool(unshift)), int(tile),
+           int(max_workgroups), C.dt(w16.dtype), C.stream())
+    return out
+
+
 # ------------------------------------------------------------------ nnU-Net (csrc/nnunet.hip)
 def _nu_volume(t, name):
     """(N, D, H, W, ld) of a contiguous channels-last 16-bit volume [N, D, H, W, ld]."""

@@ -1233,6 +1233,55 @@ int dle_upsample3d_x2_fwd(const void* x, int64_t ldx, int64_t x_off, void* y, in
 int dle_nnunet_head_blend_fwd(const void* x, int64_t ldx, const void* w, const float* b, const float* imp, float* out, int K, int C,
                               int Dp, int Hp, int Wp, int Dv, int Hv, int Wv, int d0, int h0, int w0, int dtype, hipStream_t stream);
 
+/* ---- MoFlow molecule generation, the reverse flow (csrc/moflow.hip; reference PyTorch/DrugDiscovery/MoFlow/moflow/model) ------
+ * Bond flow (Glow.reverse, glow.py:229; conv_lu == 2, one block).  The squeezed image has G x G = P <= 9 positions, so a 3x3 / pad 1
+ * convolution is the dense map [B, P Cin] x [P Cin, P Cout] of its live taps (packed on the host); layers 1 and 2 of a coupling
+ * (Conv2d + BatchNorm2d in evaluation mode + ReLU, coupling.py:59-63) run on dle_gemm with the BatchNorm folded into weight and
+ * bias in fp32 BEFORE the single rounding of the weight to 16 bits.  The flow state is fp32 [B][P][C], C = 4 fold^2 channels
+ * innermost, channel c = (e fold + fy) fold + fx of Block._squeeze (glow.py:152-170); a half is channels [0, C/2) or [C/2, C).
+ * dle_mf_squeeze_fwd: z_adj fp32 [B][4][N][N] (row pitch ldz) -> the state and the 16-bit image [B][P][C/2] of half img_half.
+ * dle_mf_couple_fwd: the third convolution of AffineCoupling (coupling.py:64) with the rest of Flow.reverse (glow.py:78-84,
+ *   coupling.py:86-100, basic.py:92-93) in its epilogue.  w3 [2 M][K], M = P C/2: row j = q C/2 + c holds s of element (q, c), row
+ *   M + j its t; b3 fp32 [2 M] likewise; h2 16-bit [B][K] (row pitch ldh).  With a / b the pass-through / updated half (b is the
+ *   first half when mask_swap):
+ *     s = acc_s + b3[j], t = acc_t + b3[M + j]                        (fp32 MFMA accumulation from 0, then the bias)
+ *     out[b half] = (in[b half] * (1 + exp(-s)) - t) / scale - loc,   out[a half] = in[a half] / scale - loc
+ *   each operation rounded to fp32 on its own (no contraction, true division); no clamp on exp: an overflow gives that element's
+ *   inf / NaN and touches nothing else.  scale, loc fp32 [C].  state_out may be state_in.  img (NULL or 16-bit [B][P][C/2]) = the
+ *   rounding of out's half img_half, what the next flow's first layer reads.  Envelope: C/2 % 4 == 0, M % 32 == 0, K % 16 == 0.
+ * dle_mf_bond_decide_fwd: MoFlow.reverse (model.py:222-229) in one pass: un-squeeze by index, h = (h + 0.5) * 2 when unshift
+ *   (noise_scale == 0), v_e = (h[e,i,j] + h[e,j,i]) / 2 in fp32, and the discretisation as a rule: bit e of mask[b,i,j] is set iff
+ *   v_e equals the maximum of the four (ties set several bits, as floor(softmax / max) does); code = the lowest set bit's index
+ *   (argmax of the 0/1 tensor).  It differs from the reference only where two softmax values round equal while the logits differ;
+ *   a NaN among the four sets no bit for it.  adj01 (NULL or fp32 [B][4][N][N]) = the reference's tensor, h_adj (NULL or fp32
+ *   [B][4][N][N]) = the un-squeezed state before the un-shift.
+ * dle_mf_atom_reverse_fwd: GlowOnGraph.reverse (glow.py:263-270) in one launch, a workgroup per tile of 32 samples, the N x T states
+ *   in LDS across all flows.  Flow i (last to first) updates row r = (i row_stride) % N only (mask_row_size == 1): the graph
+ *   convolution of row r (basic.py:187-194) regrouped as g = [sum_n adj[e,r,n] y[n,:] (n != r) for e | deg_e(r) | 0] (fp32 sums in
+ *   ascending n, rounded to 16 bits once) times [4 T + 4 -> gnn] weights, then the linear blocks and the last linear, every
+ *   BatchNorm2d(n_node) of row r (an affine per flow in evaluation mode) folded into weight and bias in fp32 before the weight's
+ *   single rounding; hidden activations are rounded to 16 bits after the ReLU, s and t stay fp32;
+ *   y[r,:] = y[r,:] * (1 + exp(-s)) - t, then y[n,:] = y[n,:] / scale[n] - loc[n] for all n (fp32, uncontracted).
+ *   w16: per flow (pitch w_stride elements) Wg [D1][KG], W1 [D2][D1], W2 [D3][D2], W3 [32][D3] (rows 0.. = s, 16.. = t), each in MFMA
+ *   fragment order [row / 32][k / 16][lane][8]; KG = 4 T + 4 rounded up to 16, D* = the widths rounded up to 32, zero padded.
+ *   p32: per flow (pitch p_stride) bg [D1], b1 [D2], b2 [D3], b3 [32], scale [N], loc [N].  mask = dle_mf_bond_decide_fwd's bits.
+ *   x fp32 [B][N][T], (x + 0.5) * 2 when unshift.  tile must be 32 (16 and 64 are not built); the grid is min(ceil(B / 32),
+ *   max_workgroups or the device's CU count when 0).  Envelope (dle_mf_atom_supported, host only, 1 / 0): one block, one gnn layer,
+ *   two linear blocks, mask_row_size 1, N <= 64, T <= 16, widths <= 512, the LDS image within 160 KB.
+ * All: no allocation, no synchronisation, graph capturable; -1 and a message, nothing launched, on a bad argument.              */
+int dle_mf_squeeze_fwd(const float* z_adj, int64_t ldz, float* state, void* img, int B, int N, int fold, int img_half, int dtype,
+                       hipStream_t stream);
+int dle_mf_couple_fwd(const void* h2, int64_t ldh, const void* w3, const float* b3, const float* scale, const float* loc,
+                      const float* state_in, float* state_out, void* img, int B, int P, int half_channels, int K, int mask_swap,
+                      int img_half, int dtype, hipStream_t stream);
+int dle_mf_bond_decide_fwd(const float* state, uint8_t* mask, uint8_t* code, float* adj01, float* h_adj, int B, int N, int fold,
+                           int unshift, hipStream_t stream);
+int dle_mf_atom_supported(int N, int T, int n_block, int n_gnn, int gnn0, int n_lin, int lin0, int lin1, int n_flow,
+                          int mask_row_size);
+int dle_mf_atom_reverse_fwd(const float* z_x, int64_t ldz, const uint8_t* mask, const void* w16, int64_t w_stride, const float* p32,
+                            int64_t p_stride, float* x, int B, int N, int T, int gnn0, int lin0, int lin1, int n_flow, int row_stride,
+                            int unshift, int tile, int max_workgroups, int dtype, hipStream_t stream);
+
 /* ---- collectives over librccl.so (csrc/rccl_comm.hip) -------------------------------------------------
  * What the reference reaches through torch.distributed's ProcessGroupNCCL: the gradient all-reduce of the DDP reducer
  * (Classification/ConvNets/image_classification/training.py:78-84), BERT's comm hook (LanguageModeling/BERT/run_pretraining.py:
