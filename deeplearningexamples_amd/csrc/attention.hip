@@ -25,6 +25,7 @@
 // Softmax statistics and accumulation are fp32; probabilities enter the MFMAs rounded to the activation dtype after the
 // dropout scaling (the reference's autocast does the same: softmax and dropout run in fp32, bmm casts its operands).
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 #include "dropout.h"
 
 #define AT_S 128
@@ -988,7 +989,7 @@ __device__ __forceinline__ void at_block_scores_masked(float16_t* s, float scale
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float x = s[kb][r] * scale;
-      s[kb][r] = (kb * 32 + (r & 3) + 8 * (r >> 2)) < remh ? x : -INFINITY;
+      s[kb][r] = (kb * 32 + rt_feat(r, 0)) < remh ? x : -INFINITY;
     }
 }
 

@@ -46,6 +46,10 @@ extern "C" void dle_set_error(const char* fmt, ...);
     else if (try_rc__ != 0) return try_rc__;  \
   } while (0)
 
+// every pointer (null included) is a multiple of `A` bytes
+template <int A, class... P>
+inline bool dle_aligned(const P*... p) { return !((... | (uintptr_t)p) & (uintptr_t)(A - 1)); }
+
 #define DLE_LAUNCH_CHECK()                                        \
   do {                                                            \
     hipError_t e__ = hipGetLastError();                           \
@@ -173,6 +177,19 @@ __device__ __forceinline__ void unpack8(ushort8_t u8, float* v) {
     }
   }
 }
+
+// c += a b^T with v_mfma_f32_32x32x16 on 16-bit fragments held as raw bits
+template <int DT> struct Mfma32x16;
+template <> struct Mfma32x16<DLE_F16> {
+  static __device__ __forceinline__ float16_t run(ushort8_t a, ushort8_t b, float16_t c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
+  }
+};
+template <> struct Mfma32x16<DLE_BF16> {
+  static __device__ __forceinline__ float16_t run(ushort8_t a, ushort8_t b, float16_t c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+  }
+};
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1): one v_exp_f32 + one v_rcp_f32.  Absolute error ~1e-7 (saturates cleanly to
 // +-1 for large |x|), far below the 16-bit rounding of every tensor it feeds.

@@ -149,9 +149,6 @@ inline bool c1d_overlap(const void* a, long long abytes, const void* b, long lon
 }
 // y may BE an addend (the lane that writes an element read it before), but not overlap it otherwise
 inline bool c1d_addend_ok(const void* add, const void* y, long long ybytes) { return add == y || !c1d_overlap(add, ybytes, y, ybytes); }
-// every pointer (null included) is a multiple of `A` bytes
-template <int A, class... P>
-inline bool c1d_aligned(const P*... p) { return !((... | (uintptr_t)p) & (uintptr_t)(A - 1)); }
 // tensors of these byte counts stay below the 4 GiB a 32-bit byte offset reaches
 template <class... N>
 inline bool c1d_under_4gib(N... bytes) { return (... && ((long long)bytes < 0xFFFFFFF0LL)); }

@@ -20,6 +20,7 @@
 //    through LDS at the end, ONE fp32 partial block per workgroup (256 workgroups: 37.7 MB whatever the layer), folded in a fixed
 //    order by a second launch (deterministic, no atomics).
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 #define W3_TG 128
 
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_kernel(W3Args p) {
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ko = kob * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+        const int ko = kob * 32 + rt_feat(r, lane >> 5);
         out[(ko * 9 + tap) * 64 + c] = acc[tap][r];
       }
   }

@@ -20,6 +20,7 @@
 // transpose read (the contraction runs over rows).  One fp32 [K][N] partial per workgroup, folded in workgroup order by
 // wgrad1x1_reduce_kernel (csrc/wgrad1x1.hip): no atomics.  Rows past M enter the product as zeros on both sides.
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 #define BB_PAD 8
 
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WG ? 2 
       for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          out[((wave * KB + kb) * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)) * TN + cb * 32 + (lane & 31)] = wacc[kb][cb][r];
+          out[((wave * KB + kb) * 32 + rt_feat(r, lane >> 5)) * TN + cb * 32 + (lane & 31)] = wacc[kb][cb][r];
   }
   if (BRED && !WG) {
     // lane fr holds value fr of its column group's 16: value i = column 32 (i >> 3) + 8 kg + (i & 7)

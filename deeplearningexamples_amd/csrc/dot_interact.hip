@@ -21,7 +21,7 @@
 //  * HBM-bound op: algorithmic bytes/sample fwd = R*C*e + OW*e, bwd = 2*R*C*e + OW*e + C*e.
 //  * shapes outside the MFMA envelope (R>32, C%16 (fwd) / C%32 (bwd) != 0, fp32) take a generic
 //    LDS kernel with fp32 FMA (still one workgroup per sample).
-#include "common.h"
+#include "mfma32_rows.h"
 
 template <int DT> struct Mfma32;
 template <> struct Mfma32<DLE_F16> {
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void dot_fwd_mfma(const unsigned short* __rest
     // 32x32 C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int i = rt_feat(r, h);
       const int j = row;
       if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
     }
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void dot_fwd_mfma_walk(const unsigned short* _
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int i = rt_feat(r, h);
       const int j = row;
       if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
     }
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(256) void gather_interact_walk(const unsigned short
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int i = rt_feat(r, h);
       const int j = row;
       if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
     }
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) void gather_interact_any(const unsigned short*
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int i = rt_feat(r, h);
       const int j = row;
       if (i < R && j < i) so[C + i * (i - 1) / 2 + j] = Elem<DT>::from_f32(acc[r]);
     }

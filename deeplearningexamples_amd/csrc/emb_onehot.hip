@@ -12,6 +12,7 @@
 // element: no float atomics, bit-reproducible.  (The register form it replaces -- emb_sgd_tiny, one gradient row in flight per
 // wavefront -- ran the eight tiny tables of criteo_f15 in 110-150 us at batch 65536: 134 MB at ~1 TB/s.)
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 #define OH_TG 64                          // samples per tile
 #define OH_D 128                          // embedding dim (columns of G): 4 blocks of 32
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(512) void emb_onehot_kernel(OhArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         // D[row][col]: lane holds col = 32 j + (lane & 31), row = 32 rb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
-        const int row = rb * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+        const int row = rb * 32 + rt_feat(r, lane >> 5);
         if (row < nrows) out[row * OH_D + c] = acc[j][r];
       }
     }

@@ -172,7 +172,7 @@ extern "C" int dle_conv1d_packed_fwd(const void* x, const void* w, const float* 
   DLE_CHECK_ARG(Ko >= 8 && Ko <= 2048 && Ko % 8 == 0, "conv1d_packed_fwd: Ko must be a multiple of 8 in [8, 2048] (got %d)", Ko);
   DLE_CHECK_ARG(ksize >= 1 && ksize <= 11 && (ksize & 1), "conv1d_packed_fwd: ksize must be odd in [1, 11] (got %d)", ksize);
   DLE_CHECK_ARG(x && w && bias && y && cu_seqlens, "conv1d_packed_fwd: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(x, w, bias, add1, y) && c1d_aligned<4>(cu_seqlens),
+  DLE_CHECK_ARG(dle_aligned<16>(x, w, bias, add1, y) && dle_aligned<4>(cu_seqlens),
                 "conv1d_packed_fwd: x, w, bias, add1 and y must be 16-byte aligned");
   const long long xbytes = (long long)total * C * 2, ybytes = (long long)total * Ko * 2;
   DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "conv1d_packed_fwd: each tensor must be smaller than 4 GiB");

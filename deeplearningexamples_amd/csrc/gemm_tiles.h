@@ -41,18 +41,6 @@ static ConvGeom make_geom(int H, int W, int C, int P, int Q, int R, int S, int s
   return g;
 }
 
-template <int DT> struct Mfma32x16;
-template <> struct Mfma32x16<DLE_F16> {
-  static __device__ __forceinline__ float16_t run(ushort8_t a, ushort8_t b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma32x16<DLE_BF16> {
-  static __device__ __forceinline__ float16_t run(ushort8_t a, ushort8_t b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(4))) short short4_t;
 #define OOB_OFF 0xFFFFFFF0u

@@ -132,7 +132,7 @@ extern "C" int dle_conv1d_lrelu_fwd(const void* x, const void* w, const float* b
                 ksize, dilation);
   if (B == 0) return 0;
   DLE_CHECK_ARG(x && w && bias && y, "conv1d_lrelu_fwd: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(x, w, bias, add1, add2, y),
+  DLE_CHECK_ARG(dle_aligned<16>(x, w, bias, add1, add2, y),
                 "conv1d_lrelu_fwd: every operand must be 16-byte aligned");
   const long long xbytes = (long long)B * T * C * 2, ybytes = (long long)B * T * Ko * 2;
   DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "conv1d_lrelu_fwd: each tensor must be smaller than 4 GiB");
@@ -197,7 +197,7 @@ extern "C" int dle_hfg_post_fwd(const void* x, const void* w, const float* bias,
   DLE_CHECK_ARG(ksize >= 1 && ksize <= HFG_POST_MAXK && (ksize & 1), "hfg_post_fwd: ksize must be odd in [1, 11] (got %d)", ksize);
   if (B == 0) return 0;
   DLE_CHECK_ARG(x && w && bias && audio, "hfg_post_fwd: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(x, w, audio) && c1d_aligned<4>(bias),
+  DLE_CHECK_ARG(dle_aligned<16>(x, w, audio) && dle_aligned<4>(bias),
                 "hfg_post_fwd: x, w and audio must be 16-byte aligned");
   DLE_CHECK_ARG(c1d_under_4gib((long long)B * T * C * 2, (long long)B * T * 4), "hfg_post_fwd: each tensor must be smaller than 4 GiB");
   const int ttiles = (T + HFG_POST_TT - 1) / HFG_POST_TT;

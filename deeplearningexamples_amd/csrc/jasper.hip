@@ -233,7 +233,7 @@ extern "C" int dle_conv1d_bn_packed_fwd(const void* x, const void* w, const floa
                 "conv1d_bn_packed_fwd: stride and dilation in {1, 2}, not both 2 (got %d, %d)", stride, dilation);
   if (total_out == 0) return 0;
   DLE_CHECK_ARG(x && w && scale && shift && y && cu_in && cu_out, "conv1d_bn_packed_fwd: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(x, w, scale, shift, residual, y) && c1d_aligned<4>(cu_in, cu_out),
+  DLE_CHECK_ARG(dle_aligned<16>(x, w, scale, shift, residual, y) && dle_aligned<4>(cu_in, cu_out),
                 "conv1d_bn_packed_fwd: x, w, scale, shift, residual and y must be 16-byte aligned");
   const long long xbytes = (long long)total_in * C * 2, ybytes = (long long)total_out * Ko * 2;
   const long long wbytes = (long long)Ko * ksize * C * 2;

@@ -4,15 +4,14 @@
 // dle_mf_couple_fwd replaces, per bond flow, the third Conv2d, chunk, exp, mul, sub, cat (coupling.py:86-100) and ActNorm.reverse
 // (basic.py:92-93).  The squeezed image has at most nine positions, so the convolution is a dense product; a wavefront owns 32
 // elements (q, c) of 32 samples and runs TWO accumulators over K, the s rows and the t rows of those elements, so that s and t of
-// an element meet in one lane and the coupling inverse needs no exchange.  Operand order as csrc/ncf.hip: the weight rows are the
-// A operand, the samples the B operand, a lane ends up with 16 elements of ONE sample (element (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-// of the block in accumulator register r).
+// an element meet in one lane and the coupling inverse needs no exchange.  Operand order and lane layout: mfma32_rows.h; the paired
+// K loop (one B fragment for two MFMAs) is this kernel's own walk.
 // dle_mf_atom_reverse_fwd replaces the whole of GlowOnGraph.reverse (38 x ~25 launches at ZINC250k sizes): no dependency between
 // samples, so a workgroup of eight wavefronts keeps the N x T states of 32 samples in LDS and walks the flows; only the weights move:
 // they stream from L2 in MFMA fragment order (1 KB per wavefront request), eight fragments requested ahead of the MFMAs that use them.
 // Measured: 1.4 ms for 38 flows at batch 512 against 25 - 29 ms for the reference's modules under autocast; the time
 // is the chain's latency (six barriers and four exposed L2 round trips per flow), not arithmetic.
-#include "gemm_tiles.h"
+#include "mfma32_rows.h"
 #include <math.h>
 
 // channel c of position p of the squeezed image -> (edge type, row, column) of the [4][N][N] tensor (glow.py:152-179)
@@ -111,10 +110,7 @@ __global__ __launch_bounds__(256) void mf_couple_kernel(MfCoupleArgs p) {
     *(float4_t*)(p.sout + base + aoff) = na;
     if (p.img) {
       const float4_t v = p.img_half == bhalf ? nb : na;
-      uint2_t o;
-      o[0] = (unsigned)Elem<DT>::from_f32(v[0]) | ((unsigned)Elem<DT>::from_f32(v[1]) << 16);
-      o[1] = (unsigned)Elem<DT>::from_f32(v[2]) | ((unsigned)Elem<DT>::from_f32(v[3]) << 16);
-      *(uint2_t*)(p.img + smp * M + j0) = o;
+      *(uint2_t*)(p.img + smp * M + j0) = rt_pack4<DT>(v[0], v[1], v[2], v[3]);
     }
   }
 }
@@ -131,8 +127,7 @@ extern "C" int dle_mf_couple_fwd(const void* h2, int64_t ldh, const void* w3, co
   DLE_CHECK_ARG(ldh >= K && ldh % 8 == 0, "mf_couple_fwd: the pitch of h2 must be a multiple of 8 and at least K");
   DLE_CHECK_ARG(mask_swap == 0 || mask_swap == 1, "mf_couple_fwd: mask_swap is 0 or 1");
   DLE_CHECK_ARG(!img || img_half == 0 || img_half == 1, "mf_couple_fwd: img_half is 0 or 1");
-  DLE_CHECK_ARG(((((uintptr_t)h2) | ((uintptr_t)w3) | ((uintptr_t)b3) | ((uintptr_t)scale) | ((uintptr_t)loc) | ((uintptr_t)state_in) |
-                  ((uintptr_t)state_out)) & 15) == 0 && (((uintptr_t)img) & 7) == 0, "mf_couple_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<16>(h2, w3, b3, scale, loc, state_in, state_out) && dle_aligned<8>(img), "mf_couple_fwd: misaligned tensor");
   const int M = P * half_channels;
   DLE_CHECK_ARG((long long)B * 2 * M < 0x7FFFFFFFLL * 4, "mf_couple_fwd: tensor too large");
   if (B == 0) return 0;
@@ -190,7 +185,7 @@ extern "C" int dle_mf_bond_decide_fwd(const float* state, uint8_t* mask, uint8_t
                                       int fold, int unshift, hipStream_t stream) {
   DLE_CHECK_ARG(state && mask && code, "mf_bond_decide_fwd: null pointer");
   DLE_CHECK_ARG(B >= 0 && N >= 1 && N <= 1024 && fold >= 1 && N % fold == 0, "mf_bond_decide_fwd: bad sizes (B %d, N %d, fold %d)", B, N, fold);
-  DLE_CHECK_ARG(((((uintptr_t)state) | ((uintptr_t)adj01) | ((uintptr_t)h_adj)) & 3) == 0, "mf_bond_decide_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<4>(state, adj01, h_adj), "mf_bond_decide_fwd: misaligned tensor");
   const long long total = (long long)B * N * N;
   DLE_CHECK_ARG(total * 4 < 0x7FFFFFFFLL, "mf_bond_decide_fwd: tensor too large");
   if (total == 0) return 0;
@@ -242,13 +237,7 @@ __device__ __forceinline__ void mf_layer(const unsigned short* __restrict__ W, i
                                          const float* __restrict__ bias, unsigned short* out, int ldo, int wave, int lane) {
   const int hf = lane >> 5, row = lane & 31, nks = K >> 4;
   for (int blk = wave; blk < nblk; blk += MF_THREADS / 64) {
-    float16_t acc;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4_t v = *(const float4_t*)(bias + 32 * blk + 8 * g + 4 * hf);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[4 * g + i] = v[i];
-    }
+    float16_t acc = rt_load16(bias, 32 * blk, hf);
     // the block's fragments arrive in groups of MF_CHUNK, the next group requested before the current one's MFMAs: the weights come
     // from L2 with a latency of microseconds, and a wavefront that waits for each load streams a few GB/s
     const ushort8_t* wp = (const ushort8_t*)W + (long long)blk * nks * 64 + lane;
@@ -267,13 +256,7 @@ __device__ __forceinline__ void mf_layer(const unsigned short* __restrict__ W, i
 #pragma unroll
       for (int u = 0; u < MF_CHUNK; ++u) cur[u] = nxt[u];
     }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      uint2_t o;
-      o[0] = (unsigned)Elem<DT>::from_f32(fmaxf(acc[4 * g], 0.f)) | ((unsigned)Elem<DT>::from_f32(fmaxf(acc[4 * g + 1], 0.f)) << 16);
-      o[1] = (unsigned)Elem<DT>::from_f32(fmaxf(acc[4 * g + 2], 0.f)) | ((unsigned)Elem<DT>::from_f32(fmaxf(acc[4 * g + 3], 0.f)) << 16);
-      *(uint2_t*)(out + row * ldo + 32 * blk + 8 * g + 4 * hf) = o;
-    }
+    rt_store16<DT, true>(out + row * ldo, 32 * blk, hf, acc);
   }
 }
 
@@ -334,19 +317,9 @@ __global__ __launch_bounds__(MF_THREADS) void mf_atom_kernel(MfAtomArgs p, MfAto
       mf_layer<DT>(W + wg + w1, p.D2, p.D3 >> 5, imga, l.lda, b2, imgb, l.ldb, wave, lane);
       __syncthreads();
       if (wave == 0) {                                 // the last linear: rows 0.. = s, 16.. = t, fp32, not rounded
-        float16_t acc;
+        const float16_t acc = rt_mma<DT>(W + wg + w1 + w2 + lane * 8, 512, imgb + row * l.ldb + hf * 8, p.D3 >> 4, rt_load16(b3, 0, hf));
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4_t v = *(const float4_t*)(b3 + 8 * g + 4 * hf);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) acc[4 * g + k] = v[k];
-        }
-        const unsigned short* wp = W + wg + w1 + w2 + lane * 8;
-        const unsigned short* xp = imgb + row * l.ldb + hf * 8;
-        const int nks = p.D3 >> 4;
-        for (int ks = 0; ks < nks; ++ks) acc = Mfma32x16<DT>::run(*(const ushort8_t*)(wp + ks * 512), *(const ushort8_t*)(xp + ks * 16), acc);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) st[row * MF_STLD + (q & 3) + 8 * (q >> 2) + 4 * hf] = acc[q];
+        for (int q = 0; q < 16; ++q) st[row * MF_STLD + rt_feat(q, hf)] = acc[q];
       }
       __syncthreads();
       // the coupling inverse on row r, ActNorm's inverse on all rows
@@ -394,8 +367,7 @@ extern "C" int dle_mf_atom_reverse_fwd(const float* z_x, int64_t ldz, const uint
   const long long pneed = a.D1 + a.D2 + a.D3 + 32 + 2 * N;
   DLE_CHECK_ARG(w_stride >= wneed && w_stride % 8 == 0 && p_stride >= pneed && p_stride % 4 == 0,
                 "mf_atom_reverse_fwd: a flow needs %lld weights (pitch a multiple of 8) and %lld fp32 values (pitch a multiple of 4)", wneed, pneed);
-  DLE_CHECK_ARG((((uintptr_t)w16) & 15) == 0 && (((uintptr_t)p32) & 15) == 0 && ((((uintptr_t)z_x) | ((uintptr_t)x)) & 3) == 0,
-                "mf_atom_reverse_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<16>(w16, p32) && dle_aligned<4>(z_x, x), "mf_atom_reverse_fwd: misaligned tensor");
   if (B == 0) return 0;
   const DleDeviceLimits* lim = dle_device_limits();
   DLE_CHECK_ARG(lim != nullptr, "mf_atom_reverse_fwd: no usable device");
@@ -404,9 +376,7 @@ extern "C" int dle_mf_atom_reverse_fwd(const float* z_x, int64_t ldz, const uint
                 lim->lds_per_block, l.bytes);
   a.z = z_x; a.mask = mask; a.w = (const unsigned short*)w16; a.p32 = p32; a.x = x; a.ldz = ldz; a.wstride = w_stride; a.pstride = p_stride;
   a.B = B; a.N = N; a.T = T; a.nflow = n_flow; a.rstride = row_stride; a.unshift = unshift;
-  long long grid = ((long long)B + MF_R - 1) / MF_R;
-  const long long cap = max_workgroups > 0 ? max_workgroups : lim->cus;
-  if (grid > cap) grid = cap;
+  const long long grid = rt_persistent_grid(((long long)B + MF_R - 1) / MF_R, max_workgroups, lim);
   if (dtype == DLE_F16) DLE_LAUNCH_LDS((mf_atom_kernel<DLE_F16>), dim3((unsigned)grid), dim3(MF_THREADS), l.bytes, stream, a, l);
   else DLE_LAUNCH_LDS((mf_atom_kernel<DLE_BF16>), dim3((unsigned)grid), dim3(MF_THREADS), l.bytes, stream, a, l);
   DLE_LAUNCH_CHECK();

@@ -3,16 +3,14 @@
 //
 // dle_ncf_score_fwd.  A sample is four table rows (64 + 64 halves for the GMF branch, 128 + 128 for the MLP branch), a
 // 256 -> 256 -> 128 -> 64 ReLU MLP and one 128-wide dot product.  One workgroup of eight wavefronts per compute unit walks tiles
-// of 64 samples.  The layers are out^T = W X^T with v_mfma_f32_32x32x16 in the operand order of csrc/tft.hip: the weight rows are
-// the A operand, the 64 samples of the tile (two halves of 32) the B operand out of an LDS row image, and a lane ends up with 16
-// output features of ONE sample: feature (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the wavefront's 32-feature block in accumulator
-// register r.  The weights are read once per workgroup: W1 (128 KB) is 64 VGPRs per lane over the eight wavefronts (wavefront w
-// owns output features 32 w .. 32 w + 31), W2 (64 KB) another 64 VGPRs (wavefront w owns feature block w & 3 for the samples of
-// half w >> 2, so each block is held twice), W3 (16 KB), the biases and the final layer's fp32 weights are in LDS.
+// of 64 samples (two halves of 32).  The layers are out^T = W X^T in the operand order and lane layout of mfma32_rows.h.  The
+// weights are read once per workgroup: W1 (128 KB) is 64 VGPRs per lane over the eight wavefronts (wavefront w owns output
+// features 32 w .. 32 w + 31), W2 (64 KB) another 64 VGPRs (wavefront w owns feature block w & 3 for the samples of half w >> 2,
+// so each block is held twice), W3 (16 KB), the biases and the final layer's fp32 weights are in LDS.
 // The rows of the NEXT tile are requested before the current tile's first MFMA and land in the X image after layer 1 has read it;
 // the indices are read one tile further ahead still, so no row address waits for an index.  Nothing of a sample but its score
 // leaves the compute unit.
-#include "gemm_tiles.h"
+#include "mfma32_rows.h"
 #include <math.h>
 
 #define NC_F 64                      // GMF factors
@@ -22,7 +20,7 @@
 #define NC_L3 64
 #define NC_R 64                      // samples per tile
 #define NC_LDX 264                   // halves per line of the 256-wide images: 528 bytes, 16 lines start in 16 different 16-byte slots
-#define NC_LDH 136                   // halves per line of the 128-wide images (as TF_LD)
+#define NC_LDH 136                   // halves per line of the 128-wide images: 272 bytes, 32 lines start in 8 different bank groups
 #define NC_THREADS 512
 
 // LDS map (bytes): X image, H1 image, H2 image, W3 image, fp32 block (b1 | b2 | b3 | wf mlp part | wf gmf part), partial dots of the
@@ -46,35 +44,6 @@ struct NcfScoreArgs {
   long long B, U, I;
   int idx64, n_partials;
 };
-
-template <int DT>
-__device__ __forceinline__ uint2_t nc_pack4(float a, float b, float c, float d) {
-  uint2_t o;
-  o[0] = (unsigned)Elem<DT>::from_f32(a) | ((unsigned)Elem<DT>::from_f32(b) << 16);
-  o[1] = (unsigned)Elem<DT>::from_f32(c) | ((unsigned)Elem<DT>::from_f32(d) << 16);
-  return o;
-}
-
-// the lane's 16 biases: features n0 + 8 g + 4 hf + 0..3 of the fp32 block in LDS, g = 0..3
-__device__ __forceinline__ float16_t nc_bias(const float* b, int n0, int hf) {
-  float16_t acc;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4_t v = *(const float4_t*)(b + n0 + 8 * g + 4 * hf);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[4 * g + i] = v[i];
-  }
-  return acc;
-}
-
-// ReLU, one rounding to 16 bits, into columns n0 + feature of the lane's line of an LDS row image
-template <int DT>
-__device__ __forceinline__ void nc_store_relu(unsigned short* line, int n0, int hf, float16_t acc) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-    *(uint2_t*)(line + n0 + 4 * hf + 8 * g) = nc_pack4<DT>(fmaxf(acc[4 * g], 0.f), fmaxf(acc[4 * g + 1], 0.f), fmaxf(acc[4 * g + 2], 0.f),
-                                                           fmaxf(acc[4 * g + 3], 0.f));
-}
 
 template <int DT>
 __global__ __launch_bounds__(NC_THREADS) void ncf_score_kernel(NcfScoreArgs p) {
@@ -187,33 +156,30 @@ __global__ __launch_bounds__(NC_THREADS) void ncf_score_kernel(NcfScoreArgs p) {
     // layer 1: wavefront w -> features 32 w .. 32 w + 31 of both halves of the tile
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      float16_t acc = nc_bias(b1s, 32 * wave, hf);
+      float16_t acc = rt_load16(b1s, 32 * wave, hf);
       const unsigned short* xrow = Xs + (s * 32 + row) * NC_LDX + hf * 8;
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) acc = Mfma32x16<DT>::run(w1f[ks], *(const ushort8_t*)(xrow + ks * 16), acc);
-      nc_store_relu<DT>(H1 + (s * 32 + row) * NC_LDX, 32 * wave, hf, acc);
+      rt_store16<DT, true>(H1 + (s * 32 + row) * NC_LDX, 32 * wave, hf, acc);
     }
     __syncthreads();
     // layer 2: wavefront w -> feature block w & 3 of half w >> 2
     {
       const int blk = wave & 3, s = wave >> 2;
-      float16_t acc = nc_bias(b2s, 32 * blk, hf);
+      float16_t acc = rt_load16(b2s, 32 * blk, hf);
       const unsigned short* xrow = H1 + (s * 32 + row) * NC_LDX + hf * 8;
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) acc = Mfma32x16<DT>::run(w2f[ks], *(const ushort8_t*)(xrow + ks * 16), acc);
-      nc_store_relu<DT>(H2 + (s * 32 + row) * NC_LDH, 32 * blk, hf, acc);
+      rt_store16<DT, true>(H2 + (s * 32 + row) * NC_LDH, 32 * blk, hf, acc);
     }
     store_rows(par ^ 1, ok_next);                      // layer 1 was the X image's last reader
     __syncthreads();
     // layer 3 (fp32 output, not rounded) and its half of the final dot product: wavefronts 0..3 -> block w & 1 of half w >> 1
     if (wave < 4) {
       const int blk = wave & 1, s = wave >> 1;
-      float16_t acc = nc_bias(b3s, 32 * blk, hf);
-      const unsigned short* wrow = W3s + (32 * blk + row) * NC_LDH + hf * 8;
-      const unsigned short* xrow = H2 + (s * 32 + row) * NC_LDH + hf * 8;
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) acc = Mfma32x16<DT>::run(*(const ushort8_t*)(wrow + ks * 16), *(const ushort8_t*)(xrow + ks * 16), acc);
-      const float16_t w = nc_bias(wfm, 32 * blk, hf);
+      const float16_t acc = rt_mma<DT>(W3s + (32 * blk + row) * NC_LDH + hf * 8, 16, H2 + (s * 32 + row) * NC_LDH + hf * 8, NC_L2 / 16,
+                                       rt_load16(b3s, 32 * blk, hf));
+      const float16_t w = rt_load16(wfm, 32 * blk, hf);
       float d = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) d = fmaf(fmaxf(acc[r], 0.f), w[r], d);
@@ -264,11 +230,9 @@ extern "C" int dle_ncf_score_fwd(const void* mf_user, const void* mf_item, const
   DLE_CHECK_ARG(max_workgroups >= 0, "ncf_score_fwd: max_workgroups must be 0 (the device's CU count) or positive");
   DLE_CHECK_ARG((loss_partials == nullptr) == (label == nullptr), "ncf_score_fwd: the labels and the loss partials go together");
   DLE_CHECK_ARG(!loss_partials || n_partials >= 1, "ncf_score_fwd: the loss needs at least one partial slot");
-  DLE_CHECK_ARG(((((uintptr_t)mf_user) | ((uintptr_t)mf_item) | ((uintptr_t)mlp_user) | ((uintptr_t)mlp_item) | ((uintptr_t)w1) |
-                  ((uintptr_t)w2) | ((uintptr_t)w3)) & 15) == 0, "ncf_score_fwd: tables and weights must be 16-byte aligned");
-  DLE_CHECK_ARG(((((uintptr_t)b1) | ((uintptr_t)b2) | ((uintptr_t)b3) | ((uintptr_t)wf) | ((uintptr_t)bf) | ((uintptr_t)label) |
-                  ((uintptr_t)logit) | ((uintptr_t)prob) | ((uintptr_t)loss_partials)) & 3) == 0 &&
-                    ((((uintptr_t)user) | ((uintptr_t)item)) & (index_bits / 8 - 1)) == 0, "ncf_score_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<16>(mf_user, mf_item, mlp_user, mlp_item, w1, w2, w3), "ncf_score_fwd: tables and weights must be 16-byte aligned");
+  DLE_CHECK_ARG(dle_aligned<4>(b1, b2, b3, wf, bf, label, logit, prob, loss_partials) &&
+                    (index_bits == 64 ? dle_aligned<8>(user, item) : dle_aligned<4>(user, item)), "ncf_score_fwd: misaligned tensor");
   if (batch == 0) {
     if (loss_partials) (void)hipMemsetAsync(loss_partials, 0, sizeof(float) * n_partials, stream);
     return 0;
@@ -277,9 +241,7 @@ extern "C" int dle_ncf_score_fwd(const void* mf_user, const void* mf_item, const
   DLE_CHECK_ARG(lim != nullptr, "ncf_score_fwd: no usable device");
   DLE_CHECK_ARG(lim->lds_per_block >= NC_LDS_BYTES, "ncf_score_fwd: the device offers %d bytes of LDS per workgroup, %d needed",
                 lim->lds_per_block, NC_LDS_BYTES);
-  long long grid = (batch + NC_R - 1) / NC_R;
-  const long long cap = max_workgroups > 0 ? max_workgroups : lim->cus;
-  if (grid > cap) grid = cap;
+  long long grid = rt_persistent_grid((batch + NC_R - 1) / NC_R, max_workgroups, lim);
   if (loss_partials && grid > n_partials) grid = n_partials;
   NcfScoreArgs a = {};
   a.mfu = (const unsigned short*)mf_user; a.mfi = (const unsigned short*)mf_item;
@@ -345,7 +307,7 @@ extern "C" int dle_ncf_rank_fwd(const float* rating, const float* label, const u
   DLE_CHECK_ARG(k >= 1 && k <= S, "ncf_rank_fwd: 1 <= k <= samples per series (got k = %d, %d per series)", k, S);
   DLE_CHECK_ARG(n_series >= 0 && n_series < 0x7FFFFFFFLL, "ncf_rank_fwd: bad series count");
   DLE_CHECK_ARG(rating && label && hits && dcg, "ncf_rank_fwd: null pointer");
-  DLE_CHECK_ARG(((((uintptr_t)rating) | ((uintptr_t)label) | ((uintptr_t)hits) | ((uintptr_t)dcg)) & 3) == 0, "ncf_rank_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<4>(rating, label, hits, dcg), "ncf_rank_fwd: misaligned tensor");
   if (n_series == 0) return 0;
   hipLaunchKernelGGL(ncf_rank_kernel, dim3((unsigned)n_series), dim3(64), 0, stream, rating, label, ignore, hits, dcg, S, k);
   DLE_LAUNCH_CHECK();

@@ -13,6 +13,7 @@
 // end of the band the lanes and the two voxel halves are merged by Chan's formula in a fixed order and ONE thread per channel
 // writes the band's partial.  No atomics, no workgroup waits on another.
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 #include <math.h>
 
 #define NU_TM 128                    // output voxels per tile
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(NU_THREADS) void nu_conv3d_in_kernel(NuConvArgs p) 
   if (l31 == 0) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int kl = kh * 32 + 8 * (i >> 2) + 4 * hf + (i & 3);
+      const int kl = kh * 32 + rt_feat(i, hf);
       float* r = red + (vh * NU_TN + kl) * 3;
       r[0] = cnt; r[1] = mean[i]; r[2] = m2[i];
     }

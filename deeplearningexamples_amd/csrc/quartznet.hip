@@ -291,7 +291,7 @@ extern "C" int dle_tcs_conv1d_packed_fwd(const void* x, const void* dw, const vo
                 "tcs_conv1d_packed_fwd: stride and dilation in {1, 2}, not both 2 (got %d, %d)", stride, dilation);
   if (total_out == 0) return 0;
   DLE_CHECK_ARG(x && dw && pw && scale && shift && y && cu_in && cu_out, "tcs_conv1d_packed_fwd: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(x, dw, pw, scale, shift, residual, y, d_out) && c1d_aligned<4>(cu_in, cu_out),
+  DLE_CHECK_ARG(dle_aligned<16>(x, dw, pw, scale, shift, residual, y, d_out) && dle_aligned<4>(cu_in, cu_out),
                 "tcs_conv1d_packed_fwd: x, dw, pw, scale, shift, residual, y and d_out must be 16-byte aligned");
   const long long xbytes = (long long)total_in * C * 2, ybytes = (long long)total_out * Ko * 2, dbytes = (long long)total_out * C * 2;
   DLE_CHECK_ARG(c1d_under_4gib(xbytes, ybytes), "tcs_conv1d_packed_fwd: each tensor must be smaller than 4 GiB");
@@ -378,7 +378,7 @@ extern "C" int dle_qn_normalize_pack_lead(const float* x, void* y, const int32_t
   DLE_CHECK_ARG(T_pad >= 1 && (long long)B * F * T_pad < (1LL << 31), "qn_normalize_pack: bad T_pad (%d)", T_pad);
   if (total == 0) return 0;
   DLE_CHECK_ARG(x && y && cu_seqlens, "qn_normalize_pack: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<16>(y) && c1d_aligned<4>(x, cu_seqlens), "qn_normalize_pack: y must be 16-byte aligned");
+  DLE_CHECK_ARG(dle_aligned<16>(y) && dle_aligned<4>(x, cu_seqlens), "qn_normalize_pack: y must be 16-byte aligned");
   const dim3 grid((unsigned)B, (unsigned)(F / 8)), block(256);
   if (dtype == DLE_F16)
     hipLaunchKernelGGL((qn_normalize_pack_kernel<DLE_F16>), grid, block, 0, stream, x, (unsigned short*)y, cu_seqlens, (long long)total, F, T_pad, lead);
@@ -460,7 +460,7 @@ extern "C" int dle_ctc_greedy_packed(const float* logits, float* logp, int32_t* 
   DLE_CHECK_ARG(n_classes >= 2 && n_classes <= 4096 && ld >= n_classes && ld <= 65536,
                 "ctc_greedy_packed: 2 <= n_classes <= 4096 and n_classes <= ld (got %d, %d)", n_classes, ld);
   DLE_CHECK_ARG(n_tokens && cu_seqlens && (total == 0 || (logits && ids && tokens)), "ctc_greedy_packed: null pointer");
-  DLE_CHECK_ARG(c1d_aligned<4>(logits, logp, ids, tokens, n_tokens, cu_seqlens), "ctc_greedy_packed: misaligned operand");
+  DLE_CHECK_ARG(dle_aligned<4>(logits, logp, ids, tokens, n_tokens, cu_seqlens), "ctc_greedy_packed: misaligned operand");
   hipLaunchKernelGGL(qn_ctc_greedy_kernel, dim3((unsigned)B), dim3(256), 0, stream, logits, logp, ids, tokens, n_tokens, cu_seqlens,
                      (long long)total, n_classes, ld);
   DLE_LAUNCH_CHECK();

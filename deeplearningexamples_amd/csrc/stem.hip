@@ -20,6 +20,7 @@
 //    workgroup, folded in a fixed order (deterministic, no atomics).
 // Packed weight layout (both kernels): w2[ko][r][s8][c4], k = r * 32 + s * 4 + c, zero where s = 7 or c = 3.
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 #define ST_PW 232                 // forward patch pixels per input row: x = -3 .. 228 (W <= 224)
 #define ST_PWG 264                // weight-gradient patch: its reads reach pixel 2 * 127 + 7 (dy pixels past Q are zero rows, but
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void stem7_fwd_kernel(StemArgs a) {
   for (int r = 0; r < 7; ++r)
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
-      const int ko = kh * 32 + 8 * (i >> 2) + 4 * blk + (i & 3);
+      const int ko = kh * 32 + rt_feat(i, blk);
       wf[r][blk] = *(const ushort8_t*)(a.w + ko * ST_K2 + r * 32 + 8 * kq);
     }
   float s1[8], s2[8];

@@ -2,13 +2,13 @@
 // the variable selection network, a whole LSTM layer and the interpretable attention of the decoder positions, one launch each.
 //
 // Hidden size 128 everywhere.  Every linear layer of the model is a [128 or 256][128] matrix against a tile of 32 rows, and all of
-// them share one building block: out^T = W X^T with v_mfma_f32_32x32x16.  The weight rows are the A operand straight from global
-// memory (16 bytes per lane and k step; the matrices, 32 - 64 KB each, stay in L2), the 32 rows of the tile are the B operand out of
-// a [32][136] LDS image, and a lane ends up with 16 output features of ONE row: feature (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of
-// the wavefront's 32-feature block in accumulator register r.  Four consecutive features per register quad: the next image is
-// written with 8-byte stores, the a and b halves of a GLU sit in the same lane, and a LayerNorm is 16 registers, one lane
-// exchange and one exchange through LDS between the four wavefronts.  Intermediates never leave the compute unit.
-#include "gemm_tiles.h"
+// them share one building block: out^T = W X^T in the operand order and lane layout of mfma32_rows.h.  The weight rows come
+// straight from global memory (16 bytes per lane and k step; the matrices, 32 - 64 KB each, stay in L2), the 32 rows of the tile
+// out of a [32][136] LDS image.  A lane holds 16 features of ONE row, so the a and b halves of a GLU sit in the same lane, and a
+// LayerNorm is 16 registers, one lane exchange and one exchange through LDS between the four wavefronts.  Intermediates never
+// leave the compute unit.  The biases are read element by element (rt_load16s): the entry points ask fp32 vectors for 4-byte
+// alignment only.
+#include "mfma32_rows.h"
 
 #define TF_H 128
 #define TF_R 32                      // rows per workgroup
@@ -19,33 +19,10 @@
 #define TF_MAXT 192                  // time steps of the attention (6 key tiles held in registers)
 #define TF_VLD 40                    // halves per V line in LDS
 
-__device__ __forceinline__ int tf_feat(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
-template <int DT>
-__device__ __forceinline__ uint2_t tf_pack4(float a, float b, float c, float d) {
-  uint2_t o;
-  o[0] = (unsigned)Elem<DT>::from_f32(a) | ((unsigned)Elem<DT>::from_f32(b) << 16);
-  o[1] = (unsigned)Elem<DT>::from_f32(c) | ((unsigned)Elem<DT>::from_f32(d) << 16);
-  return o;
-}
-
 // acc += W[n0 + 0..31][0..127] . X[0..31][0..127]^T; W is row-major with 128 columns, X an LDS row image
 template <int DT>
 __device__ __forceinline__ float16_t tf_block(const unsigned short* __restrict__ W, int n0, const unsigned short* X, int lane, float16_t acc) {
-  const unsigned short* wrow = W + (n0 + (lane & 31)) * TF_H + (lane >> 5) * 8;
-  const unsigned short* xrow = X + (lane & 31) * TF_LD + (lane >> 5) * 8;
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-    acc = Mfma32x16<DT>::run(*(const ushort8_t*)(wrow + ks * 16), *(const ushort8_t*)(xrow + ks * 16), acc);
-  return acc;
-}
-
-// the lane's 16 values, rounded, into columns n0 + feature of line (lane & 31) of an LDS row image
-template <int DT>
-__device__ __forceinline__ void tf_store_img(unsigned short* X, int n0, int lane, const float* v) {
-  unsigned short* line = X + (lane & 31) * TF_LD + n0 + 4 * (lane >> 5);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) *(uint2_t*)(line + 8 * g) = tf_pack4<DT>(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+  return rt_mma<DT>(W + (n0 + (lane & 31)) * TF_H + (lane >> 5) * 8, 16, X + (lane & 31) * TF_LD + (lane >> 5) * 8, TF_H / 16, acc);
 }
 
 __device__ __forceinline__ float tf_elu(float v) { return v > 0.f ? v : expm1f(v); }
@@ -72,9 +49,9 @@ __device__ __forceinline__ void tf_glu_ln(const unsigned short* G, const unsigne
   const int hf = lane >> 5, row = lane & 31, n0 = wave * 32;
   float16_t a, b;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    a[r] = bg[n0 + tf_feat(r, hf)];
-    b[r] = bg[TF_H + n0 + tf_feat(r, hf)];
+  for (int r = 0; r < 16; ++r) {                      // (interleaved: as two rt_load16s calls tft_grn_kernel takes 13 more VGPRs)
+    a[r] = bg[n0 + rt_feat(r, hf)];
+    b[r] = bg[TF_H + n0 + rt_feat(r, hf)];
   }
   a = tf_block<DT>(wg, n0, G, lane, a);
   b = tf_block<DT>(wg, TF_H + n0, G, lane, b);
@@ -101,16 +78,9 @@ __device__ __forceinline__ void tf_glu_ln(const unsigned short* G, const unsigne
   const float rstd = 1.f / sqrtf(var + eps);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int n = n0 + tf_feat(r, hf);
+    const int n = n0 + rt_feat(r, hf);
     outv[r] = y[r] * rstd * gamma[n] + beta[n];
   }
-}
-
-// the lane's 16 values, rounded, to columns n0 + feature of a global row
-template <int DT>
-__device__ __forceinline__ void tf_store_row(unsigned short* dst, int n0, int hf, const float* v) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) *(uint2_t*)(dst + n0 + 4 * hf + 8 * g) = tf_pack4<DT>(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
 
 // ---- dle_tft_grn_fwd: GRN.forward (modeling.py:48-77); gate mode: GLU + residual + LayerNorm (:403-405, 418-420, 426-428); the
@@ -158,35 +128,28 @@ __global__ __launch_bounds__(256) void tft_grn_kernel(TftGrnArgs p) {
         return r < p.rows ? p.ctx + (r / p.rows_per_ctx) * p.ldc : nullptr;
       });
     __syncthreads();
-    float16_t acc;
+    float16_t acc = tf_block<DT>(p.wa, n0, Xs, lane, rt_load16s(p.ba, n0, hf));
     float v[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = p.ba[n0 + tf_feat(r, hf)];
-    acc = tf_block<DT>(p.wa, n0, Xs, lane, acc);
     if (p.ctx) acc = tf_block<DT>(p.wc, n0, Cs, lane, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) v[r] = tf_elu(acc[r]);
-    tf_store_img<DT>(Hs, n0, lane, v);
+    rt_store16<DT, false>(Hs + row * TF_LD, n0, hf, v);
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = p.bi[n0 + tf_feat(r, hf)];
-    acc = tf_block<DT>(p.wi, n0, Hs, lane, acc);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = acc[r];
-    tf_store_img<DT>(Gs, n0, lane, v);
+    acc = tf_block<DT>(p.wi, n0, Hs, lane, rt_load16s(p.bi, n0, hf));
+    rt_store16<DT, false>(Gs + row * TF_LD, n0, hf, acc);
     __syncthreads();
   }
   float res[16], outv[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) res[r] = Elem<DT>::to_f32(Xs[row * TF_LD + n0 + tf_feat(r, hf)]);
+  for (int r = 0; r < 16; ++r) res[r] = Elem<DT>::to_f32(Xs[row * TF_LD + n0 + rt_feat(r, hf)]);
   tf_glu_ln<DT>(Gs, p.wg, p.bg, p.gamma, p.beta, p.eps, red, wave, lane, res, outv);
   const bool ok = row0 + row < p.rows;
-  if (ok && p.out) tf_store_row<DT>(p.out + (row0 + row) * p.ldo, n0, hf, outv);
+  if (ok && p.out) rt_store16<DT, false>(p.out + (row0 + row) * p.ldo, n0, hf, outv);
   if (p.qout) {
     for (int q = 0; q < p.nq; ++q) {
       float s = 0.f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s += outv[r] * p.wq[q * TF_H + n0 + tf_feat(r, hf)];
+      for (int r = 0; r < 16; ++r) s += outv[r] * p.wq[q * TF_H + n0 + rt_feat(r, hf)];
       s += __shfl_xor(s, 32, 64);
       if (hf == 0) qs[(wave * TF_R + row) * TF_MAXQ + q] = s;
     }
@@ -233,8 +196,7 @@ extern "C" int dle_tft_grn_fwd(const void* x, int64_t ldx, const int32_t* x_inde
                   "tft_grn_fwd: ldc must be a multiple of 8, at least 128, and rows_per_ctx >= 1");
   }
   DLE_CHECK_ARG(!qout || (wq && bq && nq >= 1 && nq <= TF_MAXQ), "tft_grn_fwd: the quantile tail needs wq, bq and 1 <= nq <= 8");
-  DLE_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)ctx) | ((uintptr_t)res) | ((uintptr_t)wa) | ((uintptr_t)wc) | ((uintptr_t)wi) |
-                  ((uintptr_t)wg) | ((uintptr_t)out)) & 15) == 0, "tft_grn_fwd: tensors must be 16-byte aligned");
+  DLE_CHECK_ARG(dle_aligned<16>(x, ctx, res, wa, wc, wi, wg, out), "tft_grn_fwd: tensors must be 16-byte aligned");
   if (rows == 0) return 0;
   TftGrnArgs a = {};
   a.x = (const unsigned short*)x; a.ldx = ldx; a.xidx = x_index; a.n_xrows = n_x_rows;
@@ -306,7 +268,7 @@ __global__ __launch_bounds__(256) void tft_vsn_kernel(TftVsnArgs p) {
   // joint network: first linear folded, + lin_c(context), ELU, lin_i
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int n = n0 + tf_feat(r, hf);
+    const int n = n0 + rt_feat(r, hf);
     float s = jv[n];
     for (int f = 0; f < F; ++f) s = fmaf(xs[row * TF_MAXF + f], ju[f * TF_H + n], s);
     acc[r] = s;
@@ -314,21 +276,15 @@ __global__ __launch_bounds__(256) void tft_vsn_kernel(TftVsnArgs p) {
   if (p.ctx) acc = tf_block<DT>(wc, n0, Cs, lane, acc);
 #pragma unroll
   for (int r = 0; r < 16; ++r) v[r] = tf_elu(acc[r]);
-  tf_store_img<DT>(Hs, n0, lane, v);
+  rt_store16<DT, false>(Hs + row * TF_LD, n0, hf, v);
   __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = jbi[n0 + tf_feat(r, hf)];
-  acc = tf_block<DT>(jwi, n0, Hs, lane, acc);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = acc[r];
-  tf_store_img<DT>(Gs, n0, lane, v);
+  acc = tf_block<DT>(jwi, n0, Hs, lane, rt_load16s(jbi, n0, hf));
+  rt_store16<DT, false>(Gs + row * TF_LD, n0, hf, acc);
   __syncthreads();
   // joint GLU (2F outputs in one padded 32-row block; every wavefront computes it, so nothing is exchanged), the folded out_proj
   // residual, LayerNorm over F (Identity when F == 1, MaybeLayerNorm) and the softmax
   {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = jbg[tf_feat(r, hf)];
-    acc = tf_block<DT>(jwg, 0, Gs, lane, acc);
+    acc = tf_block<DT>(jwg, 0, Gs, lane, rt_load16s(jbg, 0, hf));
     float g[TF_MAXF];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -383,18 +339,14 @@ __global__ __launch_bounds__(256) void tft_vsn_kernel(TftVsnArgs p) {
     float res[16], outv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int n = n0 + tf_feat(r, hf);
+      const int n = n0 + rt_feat(r, hf);
       v[r] = tf_elu(fmaf(xf, vu[n], vv[n]));
       res[r] = fmaf(xf, va[n], vb[n]);
     }
-    tf_store_img<DT>(Hs, n0, lane, v);
+    rt_store16<DT, false>(Hs + row * TF_LD, n0, hf, v);
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = bi[n0 + tf_feat(r, hf)];
-    acc = tf_block<DT>(wi, n0, Hs, lane, acc);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = acc[r];
-    tf_store_img<DT>(Gs, n0, lane, v);
+    acc = tf_block<DT>(wi, n0, Hs, lane, rt_load16s(bi, n0, hf));
+    rt_store16<DT, false>(Gs + row * TF_LD, n0, hf, acc);
     __syncthreads();
     tf_glu_ln<DT>(Gs, wg, bg, gam, bet, p.eps, red, wave, lane, res, outv);
     const float w = wsel[row * TF_MAXF + f];
@@ -402,7 +354,7 @@ __global__ __launch_bounds__(256) void tft_vsn_kernel(TftVsnArgs p) {
     for (int r = 0; r < 16; ++r) o[r] = fmaf(w, outv[r], o[r]);
   }
   const long long r = row0 + row;
-  if (r < p.rows) tf_store_row<DT>(p.out + ((r / p.tn) * p.out_T + p.out_t0 + r % p.tn) * p.ldo, n0, hf, o);
+  if (r < p.rows) rt_store16<DT, false>(p.out + ((r / p.tn) * p.out_T + p.out_t0 + r % p.tn) * p.ldo, n0, hf, o);
 }
 
 extern "C" int dle_tft_vsn_fwd(const float* x0, int64_t ld0, int n0, const float* x1, int64_t ld1, int n1, const float* x2, int64_t ld2,
@@ -424,8 +376,7 @@ extern "C" int dle_tft_vsn_fwd(const float* x0, int64_t ld0, int n0, const float
   DLE_CHECK_ARG(w16 && p32 && out, "tft_vsn_fwd: null pointer");
   DLE_CHECK_ARG(ldo >= TF_H && (ldo & 7) == 0, "tft_vsn_fwd: ldo must be a multiple of 8, at least 128");
   DLE_CHECK_ARG(!ctx || (ldc >= TF_H && (ldc & 7) == 0), "tft_vsn_fwd: ldc must be a multiple of 8, at least 128");
-  DLE_CHECK_ARG(((((uintptr_t)ctx) | ((uintptr_t)w16) | ((uintptr_t)out)) & 15) == 0 &&
-                    ((((uintptr_t)x0) | ((uintptr_t)x1) | ((uintptr_t)x2) | ((uintptr_t)p32) | ((uintptr_t)weights)) & 3) == 0,
+  DLE_CHECK_ARG(dle_aligned<16>(ctx, w16, out) && dle_aligned<4>(x0, x1, x2, p32, weights),
                 "tft_vsn_fwd: 16-bit tensors must be 16-byte aligned, fp32 tensors 4-byte aligned");
   if (rows == 0) return 0;
   TftVsnArgs a = {};
@@ -479,7 +430,7 @@ __global__ __launch_bounds__(512) void tft_lstm_kernel(TftLstmArgs p) {
   float c[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const long long at = (long long)bc * TF_H + u0 + (r & 3) + 8 * (r >> 2);
+    const long long at = (long long)bc * TF_H + u0 + rt_feat(r, 0);
     c[r] = p.c0_f32 ? ((const float*)p.c0)[at] : Elem<DT>::to_f32(((const unsigned short*)p.c0)[at]);
   }
   const float* xrow = p.xp + (long long)bc * p.xp_bs + u0;
@@ -525,7 +476,7 @@ __global__ __launch_bounds__(512) void tft_lstm_kernel(TftLstmArgs p) {
     }
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      hp[g] = tf_pack4<DT>(h[4 * g], h[4 * g + 1], h[4 * g + 2], h[4 * g + 3]);
+      hp[g] = rt_pack4<DT>(h[4 * g], h[4 * g + 1], h[4 * g + 2], h[4 * g + 3]);
       *(uint2_t*)(nxt + row * TF_LD + u0 + 8 * g) = hp[g];
       if (ok && p.out) *(uint2_t*)(p.out + (long long)b * p.out_bs + (long long)t * p.out_ts + u0 + 8 * g) = hp[g];
     }
@@ -537,7 +488,7 @@ __global__ __launch_bounds__(512) void tft_lstm_kernel(TftLstmArgs p) {
       if (p.hn) *(uint2_t*)(p.hn + (long long)b * TF_H + u0 + 8 * g) = hp[g];
     if (p.cn) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) p.cn[(long long)b * TF_H + u0 + (r & 3) + 8 * (r >> 2)] = c[r];
+      for (int r = 0; r < 8; ++r) p.cn[(long long)b * TF_H + u0 + rt_feat(r, 0)] = c[r];
     }
   }
 }
@@ -557,8 +508,7 @@ extern "C" int dle_tft_lstm_fwd(const float* xproj, int64_t xp_batch_stride, int
   DLE_CHECK_ARG(!out || (out_step_stride >= TF_H && (out_step_stride & 3) == 0 && (out_batch_stride & 3) == 0 &&
                          (B == 1 || out_batch_stride >= TF_H)),
                 "tft_lstm_fwd: the output's strides must be multiples of 4, at least 128");
-  DLE_CHECK_ARG(((((uintptr_t)xproj) | ((uintptr_t)whh) | ((uintptr_t)h0) | ((uintptr_t)c0) | ((uintptr_t)cn)) & 15) == 0 &&
-                    ((((uintptr_t)out) | ((uintptr_t)hn)) & 7) == 0, "tft_lstm_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<16>(xproj, whh, h0, c0, cn) && dle_aligned<8>(out, hn), "tft_lstm_fwd: misaligned tensor");
   TftLstmArgs a = {};
   a.xp = xproj; a.xp_bs = xp_batch_stride; a.xp_ts = xp_step_stride; a.whh = (const unsigned short*)whh;
   a.h0 = (const unsigned short*)h0; a.c0 = c0; a.c0_f32 = c0_dtype == DLE_F32;
@@ -626,7 +576,7 @@ __global__ __launch_bounds__(64) void tft_attn_kernel(TftAttnArgs p) {
         for (int ks = 0; ks < 2; ++ks) s[kt] = Mfma32x16<DT>::run(*(const ushort8_t*)(krow + ks * 16), qf[ks], s[kt]);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int j = kt * 32 + tf_feat(r, hf);
+          const int j = kt * 32 + rt_feat(r, hf);
           s[kt][r] = j <= ic ? s[kt][r] * p.scale : -INFINITY;
           m = fmaxf(m, s[kt][r]);
         }
@@ -660,7 +610,7 @@ __global__ __launch_bounds__(64) void tft_attn_kernel(TftAttnArgs p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       pm[kt][r] = kt < ntiles ? pm[kt][r] * 0.25f : 0.f;
-      const int j = kt * 32 + tf_feat(r, hf);
+      const int j = kt * 32 + rt_feat(r, hf);
       if (p.probs && qok && j < p.T) p.probs[orow * p.T + j] = pm[kt][r];
     }
   }
@@ -680,7 +630,7 @@ __global__ __launch_bounds__(64) void tft_attn_kernel(TftAttnArgs p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           pv[e] = pm[kt][8 * ks + e];
-          vf[e] = Vs[(kt * 32 + 16 * ks + 8 * (e >> 2) + 4 * hf + (e & 3)) * TF_VLD + qi];
+          vf[e] = Vs[(kt * 32 + 16 * ks + rt_feat(e, hf)) * TF_VLD + qi];
         }
         ctx = Mfma32x16<DT>::run(vf, pack8<DT>(pv), ctx);
       }
@@ -708,12 +658,7 @@ __global__ __launch_bounds__(64) void tft_attn_kernel(TftAttnArgs p) {
       w4[0] = lo[0]; w4[1] = lo[1]; w4[2] = hi[0]; w4[3] = hi[1];
       o = Mfma32x16<DT>::run(__builtin_bit_cast(ushort8_t, w4), cf[ks], o);
     }
-    if (qok) {
-      float ov[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ov[r] = o[r];
-      tf_store_row<DT>(p.out + orow * TF_H, nb * 32, hf, ov);
-    }
+    if (qok) rt_store16<DT, false>(p.out + orow * TF_H, nb * 32, hf, o);
   }
 }
 
@@ -725,8 +670,7 @@ extern "C" int dle_tft_attention_fwd(const void* qkv, int64_t ld, const void* wo
   DLE_CHECK_ARG(encoder_length >= 1 && encoder_length < T, "tft_attention_fwd: 1 <= encoder_length < T (got %d, %d)", encoder_length, T);
   DLE_CHECK_ARG(qkv && wo && out, "tft_attention_fwd: null pointer");
   DLE_CHECK_ARG(ld >= 9 * 32 && (ld & 7) == 0, "tft_attention_fwd: ld must be a multiple of 8, at least 288");
-  DLE_CHECK_ARG(((((uintptr_t)qkv) | ((uintptr_t)wo) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)probs) & 3) == 0,
-                "tft_attention_fwd: misaligned tensor");
+  DLE_CHECK_ARG(dle_aligned<16>(qkv, wo, out) && dle_aligned<4>(probs), "tft_attention_fwd: misaligned tensor");
   const int nq = T - encoder_length, nqt = (nq + 31) / 32;
   DLE_CHECK_ARG((long long)B * nqt < 0x7FFFFFFFLL, "tft_attention_fwd: grid too large");
   TftAttnArgs a = {};

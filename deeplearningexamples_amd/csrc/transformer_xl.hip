@@ -21,6 +21,7 @@
 //  * ring rows at or past the logical window, distances outside the table and queries past qlen are SELECTED to zero when they
 //    are loaded and the scores outside the band are selected to -inf: what those rows hold never reaches an MFMA.
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 #define TX_D 64
 #define TX_T 32                       // queries per workgroup = keys per tile
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(256) void txl_rel_attn_kernel(TxlAttnArgs p) {
 #pragma unroll
       for (int eb = 0; eb < 2; ++eb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) G[qi * TX_GLD + eb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf] = g[eb][r];
+        for (int r = 0; r < 16; ++r) G[qi * TX_GLD + eb * 32 + rt_feat(r, hf)] = g[eb][r];
       // V tile -> swizzled [32 keys][64] image; keys at or past klen are zero whatever the ring holds there
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) {
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(256) void txl_rel_attn_kernel(TxlAttnArgs p) {
       float v = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int kj = (r & 3) + 8 * (r >> 2) + 4 * hf, j = j0 + kj;
+        const int kj = rt_feat(r, hf), j = j0 + kj;
         const float x = (s[r] + G[qi * TX_GLD + qi + (TX_T - 1) - kj]) * p.scale;
         const bool ok = qok && (i - p.shift < j) && (j <= i + p.mlen) && (j < p.klen);
         s[r] = ok ? x : -INFINITY;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void txl_rel_attn_kernel(TxlAttnArgs p) {
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) G[qi * TX_GLD + db * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf] = o[db][r] * f;
+    for (int r = 0; r < 16; ++r) G[qi * TX_GLD + db * 32 + rt_feat(r, hf)] = o[db][r] * f;
   __syncthreads();
   {
     const int qo = tid >> 3, c = tid & 7;

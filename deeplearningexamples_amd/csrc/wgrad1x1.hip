@@ -12,6 +12,7 @@
 //    source address) so that the 4 rows a read group touches cover all banks;
 //  * one fp32 partial block per workgroup (256 / 512 of them: 16-64 MB instead of the operands again), folded in a fixed order.
 #include "gemm_tiles.h"
+#include "mfma32_rows.h"
 
 struct W1Args {
   const unsigned short* G;     // dy [M, Ko]
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(512) void wgrad1x1_kernel(W1Args p) {
         const int c = (wn * WN + j) * 32 + (lane & 31);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ko = (wm * WM + i) * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+          const int ko = (wm * WM + i) * 32 + rt_feat(r, lane >> 5);
           out[ko * CC + c] = acc[i][j][r];
         }
       }
